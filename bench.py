@@ -23,10 +23,17 @@ W untimed warmup steps, then EXACTLY K steps bracketed by barrier + device synch
 both sides; the MAX step time over ranks is reported.  Per-GPU batch is fixed as N grows
 (weak scaling).  The reference publishes no numbers, so the baseline is stock PyTorch-ROCm
 running the reference's mechanics (torch DDP, foreach SGD, torch.amp.GradScaler: ``--impl
-torch``) on the SAME box: after the native run, a fresh child job measures it with the same
-model, batch, dtype and steps (``--stock-baseline``), and ``vs_baseline`` = value / that number.
-The round-1 constant from another box stays in the record as
-``baseline.stock_reference_constant`` and is the divisor only when the child job fails.
+torch``) on the SAME box: with ``--full``, after the native run, a fresh child job measures it
+with the same model, batch, dtype and steps (``--stock-baseline``), and ``vs_baseline`` = value /
+that number.  The round-1 constant from another box stays in the record as
+``baseline.stock_reference_constant`` and is the divisor in a plain run and when the child job fails.
+
+A plain run (no ``--full``) does only what the headline needs: set-up, W warmup steps, the K
+timed steps, ``--dump-outputs``, the record.  ``--full`` adds the profiled second window
+(N > 1), the stock child job and the extra windows (other models and precisions), as before.
+``--dump-outputs DIR`` writes what the last timed step computed (``dump_outputs``); model
+initialisation and the batch pool are seeded, so two builds run with the same arguments see the
+same inputs and their files can be compared one by one.
 """
 from __future__ import annotations
 
@@ -81,9 +88,18 @@ def parse(argv=None):
                          "framework's, env DPT_CONV_STREAMK)")
     ap.add_argument("--no-weight-shadow", action="store_true",
                     help="A/B: autocast casts fp32 weights every forward (no optimizer-kept bf16 copy)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline window, also measure everything else this script knows: the "
+                         "profiled second window (--profile-steps), the same-box stock run (--stock-baseline) "
+                         "and the extra windows (--extra-windows).  Without it the job sets up, warms up, times "
+                         "--steps steps, writes --dump-outputs and prints the record; those three options "
+                         "only choose what --full runs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned and left behind "
+                         "(logits, loss, parameters, buffers) as DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--profile-steps", type=int, default=8,
-                    help="a SECOND timed window of this many steps, after the headline window, with "
-                         "per-bucket hipEvents on the comm stream (one event slot per step, read after "
+                    help="with --full: a SECOND timed window of this many steps, after the headline window, "
+                         "with per-bucket hipEvents on the comm stream (one event slot per step, read after "
                          "the window: no host sync inside it) -> BASELINE's second metric, %% of step "
                          "in all-reduce, plus exposed comm; 0 = off")
     ap.add_argument("--comm", default="rccl", choices=["rccl", "c10d", "host", "host-async"],
@@ -104,15 +120,15 @@ def parse(argv=None):
                          "created and the reducer fell back to torch's c10d communicator (default: exit 4 "
                          "without measuring - a headline must come from the framework's RCCL reducer)")
     ap.add_argument("--stock-baseline", default="auto", choices=["auto", "on", "off"],
-                    help="after the native run, measure stock PyTorch-ROCm (--impl torch: torch DDP, foreach "
-                         "SGD, torch.amp.GradScaler) with the same model/batch/dtype/steps in a FRESH child "
+                    help="with --full: after the native run, measure stock PyTorch-ROCm (--impl torch: torch DDP, "
+                         "foreach SGD, torch.amp.GradScaler) with the same model/batch/dtype/steps in a FRESH child "
                          "job on the same GPUs; vs_baseline is then value / that number (auto: on for the "
                          "native engine on GPUs)")
     ap.add_argument("--stock-timeout", type=float, default=420.0,
                     help="seconds the stock child job may take before it is killed (then no same-box number)")
     ap.add_argument("--extra-windows", default="auto", choices=["auto", "on", "off"],
-                    help="after the headline (and the stock job), fresh child jobs on the same GPUs for "
-                         "BASELINE.json configs 4 and 5: at 1 GPU the ViT-B/16 bf16 AdamW step and the fp32 "
+                    help="with --full: after the headline (and the stock job), fresh child jobs on the same GPUs "
+                         "for BASELINE.json configs 4 and 5: at 1 GPU the ViT-B/16 bf16 AdamW step and the fp32 "
                          "ResNet-50 step, at 4 GPUs the fp32 ResNet-50 run (AMP vs FP32 with the sync "
                          "profile), at 8 GPUs ViT-B/16 at several bucket caps; recorded under extra_windows, "
                          "never part of the headline (auto: on for the native ResNet-50 bf16 engine on 1, 4 "
@@ -536,7 +552,8 @@ def extra_windows_plan(a, ws: int, forced: bool = False) -> list:
     ``forced`` (--extra-windows on) adds the fp32 window at any world size."""
     common = ["--gpus", str(ws), "--stock-baseline", "off", "--extra-windows", "off", "--comm", a.comm,
               "--bucket-cap-mb", str(a.bucket_cap_mb)]
-    steps = ["--steps", str(a.extra_steps), "--warmup", "3", "--profile-steps", "6"]
+    # --full for the window's own profiled second window (its child jobs are switched off in ``common``)
+    steps = ["--steps", str(a.extra_steps), "--warmup", "3", "--full", "--profile-steps", "6"]
     r50_shape = ["--model", a.model, "--batch-size", str(a.batch_size), "--image-size", str(a.image_size)]
     plan = []
     vit1 = ("vit_b16_bucket25mb", common[:-1] + ["25", "--model", "vit_b_16", "--batch-size", "128",
@@ -576,6 +593,50 @@ def run_stock_baseline(a, timeout: float) -> dict:
                 "wall_s": rec["wall_s"], "cmd": "bench.py " + " ".join(_stock_argv(a, None))}
     except KeyError as e:
         return {"error": repr(e)[:400]}
+
+
+DUMP_SAMPLE = 4 << 20     # elements kept of a flat array longer than this (16 MiB as float32)
+
+
+def _dump_sample(flat: torch.Tensor) -> torch.Tensor:
+    """``flat`` itself, or - past DUMP_SAMPLE elements - the elements at a fixed set of positions
+    (sorted, drawn without replacement from a generator seeded with 0: the same positions for the
+    same length in every run and every build)."""
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        return flat
+    g = torch.Generator(device="cpu")
+    g.manual_seed(0)
+    idx = torch.randperm(n, generator=g)[:DUMP_SAMPLE].sort().values
+    return flat[idx]
+
+
+def dump_outputs(path: str, trainer, last) -> dict:
+    """Write what the last timed step computed as ``path/<name>.npy`` (float32 unless noted):
+
+    * ``logits`` - the model outputs ``train_step`` returned, ``loss`` - the loss it returned;
+    * ``params`` - every trainable parameter after the step's update, flattened in
+      ``named_parameters`` order (a fixed seeded sample when there are more than DUMP_SAMPLE
+      elements: ResNet-50 has 25.6 M), ``param_norms`` (float64) - the L2 norm of each whole tensor;
+    * ``buffers`` - the floating-point buffers (BatchNorm running statistics), same order and rule.
+
+    At most 3 x 16 MiB + the small arrays.  Returns {name: shape} for the record."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    outputs, loss = last
+    module = trainer.module
+    out = {"logits": outputs.detach().float().cpu(), "loss": loss.detach().float().reshape(1).cpu()}
+    params = [p.detach().float().reshape(-1).cpu() for _, p in module.named_parameters()]
+    bufs = [b.detach().float().reshape(-1).cpu() for _, b in module.named_buffers() if b.is_floating_point()]
+    out["params"] = _dump_sample(torch.cat(params))
+    out["param_norms"] = torch.stack([p.double().norm() for p in params])
+    if bufs:
+        out["buffers"] = _dump_sample(torch.cat(bufs))
+    if out["logits"].numel() > DUMP_SAMPLE:      # keeps its shape unless it has to be sampled
+        out["logits"] = _dump_sample(out["logits"].reshape(-1))
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
+    return {name: list(t.shape) for name, t in out.items()}
 
 
 def train_args(a):
@@ -690,9 +751,12 @@ def main(argv=None) -> int:
     batches = list(iter(loader))
 
     def run(n):
+        last = None
         for i in range(n):
             x, y = batches[i % len(batches)]
-            trainer.train_step(x, y)
+            # (outputs, loss) for --dump-outputs, detached: the step's autograd graph dies here, as before
+            last = tuple(t.detach() for t in trainer.train_step(x, y))
+        return last
 
     def fence():
         if ws > 1:
@@ -704,9 +768,11 @@ def main(argv=None) -> int:
     fence()
     warm_s = time.time() - t_w
     t0 = time.time()
-    run(a.steps)
+    last = run(a.steps)
     fence()
     dt = own_dt = time.time() - t0
+    dumped = dump_outputs(a.dump_outputs, trainer, last) if (a.dump_outputs and rank == 0 and last) else None
+    del last
     if ws > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=_red_dev(device))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -717,7 +783,7 @@ def main(argv=None) -> int:
 
     prof, prof_window = {}, None
     collective = ws > 1 and a.impl == "native" and trainer.ddp is not None and trainer.ddp.comm is not None
-    if a.profile_steps > 0 and collective and device.type == "cuda" and trainer.graphed is None:
+    if a.full and a.profile_steps > 0 and collective and device.type == "cuda" and trainer.graphed is None:
         # second timed window, per-bucket comm events on: one event slot per step, everything
         # read after the window (every rank runs the same steps)
         trainer.timeline.enabled = True
@@ -767,6 +833,8 @@ def main(argv=None) -> int:
                      "stock_reference_constant_source": "BASELINE.md round-1 stock run x N (another box)",
                      "stock_same_box_img_s": None, "vs_baseline_source": "stock_reference_constant"},
         "warmup_seconds": round(warm_s, 1),
+        "full": bool(a.full),
+        "dump_outputs": dumped,     # {file name: shape} written under --dump-outputs, else null
     }
     # BASELINE's second headline number, measured in the second (profiled) window; null when
     # there is no collective (one GPU: the reducer runs local) or it was not measured
@@ -805,13 +873,14 @@ def main(argv=None) -> int:
     if ws > 1:
         dist.barrier()
     trainer.close()
-    stock_on = a.stock_baseline == "on" or (a.stock_baseline == "auto" and a.impl == "native"
-                                            and device.type == "cuda" and not a.rehearse_shared_gpu
-                                            and not a.fake_pg)
-    extra_on = a.extra_windows == "on" or (a.extra_windows == "auto" and a.impl == "native"
-                                            and device.type == "cuda" and not a.rehearse_shared_gpu
-                                            and not a.fake_pg and a.model == "resnet50" and not a.no_amp
-                                            and ws in (1, 4, 8))
+    # child jobs only under --full: a plain run ends with its headline
+    stock_on = a.full and (a.stock_baseline == "on" or (a.stock_baseline == "auto" and a.impl == "native"
+                                                        and device.type == "cuda" and not a.rehearse_shared_gpu
+                                                        and not a.fake_pg))
+    extra_on = a.full and (a.extra_windows == "on" or (a.extra_windows == "auto" and a.impl == "native"
+                                                       and device.type == "cuda" and not a.rehearse_shared_gpu
+                                                       and not a.fake_pg and a.model == "resnet50" and not a.no_amp
+                                                       and ws in (1, 4, 8)))
     extra_plan = extra_windows_plan(a, ws, forced=a.extra_windows == "on") if extra_on else []
     t_dead = deadline_at(a)
     printed = []

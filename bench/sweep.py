@@ -34,7 +34,8 @@ TABLES = {
 def run_point(extra, steps, warmup, out, timeout, launcher=None, find=True):
     # --find: MIOpen find mode (cudnn.benchmark).  Off = immediate mode over the shipped find-db
     # (bf16 shapes); fp32 shapes then use MIOpen's heuristics instead of minutes of searching.
-    cmd = (launcher or [sys.executable]) + [os.path.join(ROOT, "bench.py"), "--steps", str(steps),
+    # --full: the "vs stock" column is the same-box stock child job of each point
+    cmd = (launcher or [sys.executable]) + [os.path.join(ROOT, "bench.py"), "--full", "--steps", str(steps),
                                             "--warmup", str(warmup), "--json-out", out] + \
         (["--find"] if find else []) + extra
     print("+", " ".join(cmd), flush=True)

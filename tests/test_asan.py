@@ -36,7 +36,9 @@ def test_reducer_under_address_sanitizer(tmp_path):
                             "print(ops.native().__file__)"], env=env, capture_output=True, text=True,
                            cwd=tmp_path, timeout=300)
     assert probe.returncode == 0 and str(so) in probe.stdout, probe.stdout + probe.stderr
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider",
+    # --rootdir: run from tmp_path, pytest would otherwise take the common ancestor of tmp_path and
+    # the checkout as its root and collect from there down, through directories it may not read
+    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", "--rootdir", ROOT,
                         os.path.join(ROOT, "tests", "test_ddp_gloo.py"),
                         os.path.join(ROOT, "tests", "test_watchdog.py")],
                        env=env, capture_output=True, text=True, cwd=tmp_path, timeout=1200)

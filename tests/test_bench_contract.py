@@ -149,7 +149,7 @@ def test_bench_same_box_stock_baseline(tmp_path, n):
     """the record carries a stock (--impl torch) number measured by a fresh
     child job of the same shape right after the native run, and vs_baseline divides by it."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--stock-baseline", "on",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--full", "--stock-baseline", "on",
                         *TINY], cwd=tmp_path, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
@@ -200,13 +200,89 @@ def test_bench_no_fallback_reason_without_fallback(tmp_path):
     assert _json_lines(r.stdout)[0]["comm"]["fallback_reason"] is None
 
 
+def _load_dump(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
+
+
+def test_bench_plain_run_dumps_outputs_and_starts_no_child_job(tmp_path):
+    """A plain run (no --full) ends with its headline even when the child-job options are on, and
+    --dump-outputs writes the last timed step's arrays; a second run with the same arguments sees
+    the same inputs, so it writes the same arrays (CPU: same kernels, same thread count)."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stock-baseline", "on",
+                            "--extra-windows", "on", "--dump-outputs", str(d), *TINY], cwd=tmp_path,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = _json_lines(r.stdout)[0]
+        _check(rec, 1)
+        assert rec["full"] is False and "extra_windows" not in rec and "stock_same_box" not in rec["baseline"]
+        assert "headline measured" not in r.stderr
+        dumps.append(_load_dump(d))
+        assert rec["dump_outputs"] == {k_: list(v.shape) for k_, v in dumps[-1].items()}
+    a, b = dumps
+    assert sorted(a) == ["buffers", "logits", "loss", "param_norms", "params"]
+    assert a["logits"].shape == (4, 10) and a["loss"].shape == (1,)
+    n_params = 11181642                                            # ResNet-18 with 10 classes
+    assert a["params"].shape == (4 << 20,) and a["param_norms"].shape == (62,) and n_params > 4 << 20
+    for name, v in a.items():
+        assert v.dtype == (np.float64 if name == "param_norms" else np.float32), (name, v.dtype)
+        assert np.isfinite(v).all(), name
+        np.testing.assert_allclose(v, b[name], rtol=1e-5, atol=1e-6, err_msg=name)
+    # the sample is of the trained parameters: its norm is the matching share of the whole
+    whole = float(np.sqrt((a["param_norms"] ** 2).sum()))
+    part = float(np.sqrt((a["params"].astype(np.float64) ** 2).sum()))
+    assert part == pytest.approx(whole * ((4 << 20) / n_params) ** 0.5, rel=0.05)
+
+
+def test_dump_sample_positions_are_fixed():
+    import importlib.util
+
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    small = torch.arange(10.0)
+    assert bench._dump_sample(small) is small
+    n = bench.DUMP_SAMPLE + 1000
+    big = torch.arange(n, dtype=torch.float32)
+    s1, s2 = bench._dump_sample(big), bench._dump_sample(big.clone())
+    assert s1.numel() == bench.DUMP_SAMPLE and torch.equal(s1, s2)
+    assert bool((s1[1:] > s1[:-1]).all()) and s1[-1] < n           # distinct positions, in order
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_native_step(tmp_path):
+    """--dump-outputs on the native engine's step (ResNet-50, bf16): the arrays a caller of the
+    step gets, a fixed-size sample of the 25.6 M parameters, well under 64 MB in all."""
+    import numpy as np
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch-size", "32",
+                        "--image-size", "64", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)],
+                       cwd=tmp_path, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = _json_lines(r.stdout)[0]
+    assert rec["steps"] == 2 and rec["config"]["impl"] == "native" and rec["config"]["native_conv"] is True
+    a = _load_dump(d)
+    assert sorted(a) == ["buffers", "logits", "loss", "param_norms", "params"]
+    assert a["logits"].shape == (32, 1000) and a["params"].shape == (4 << 20,)
+    assert a["param_norms"].shape == (161,) and a["buffers"].size >= 2 * 26560      # BN running statistics
+    assert sum(v.nbytes for v in a.values()) < 64e6
+    for name, v in a.items():
+        assert v.dtype == (np.float64 if name == "param_norms" else np.float32) and np.isfinite(v).all(), name
+    assert float(a["loss"][0]) > 0 and float(a["logits"].std()) > 0
+
+
 @pytest.mark.gpu
 def test_bench_self_launch_two_ranks_on_one_gpu(tmp_path):
     """The self-launch path on a real GPU: ``bench.py --gpus 2 --rehearse-shared-gpu`` without
     torchrun runs 2 rank processes on cuda:0 (gloo control plane, host-bridge collective)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch-size", "32",
-           "--image-size", "64", "--steps", "2", "--warmup", "1", "--profile-steps", "2",
+           "--image-size", "64", "--steps", "2", "--warmup", "1", "--full", "--profile-steps", "2",
            "--rehearse-shared-gpu"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -230,7 +306,7 @@ def test_bench_two_ranks_sharing_one_gpu(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--batch-size", "32", "--image-size", "64", "--steps", "2", "--warmup", "1",
-           "--profile-steps", "2", "--rehearse-shared-gpu"]
+           "--full", "--profile-steps", "2", "--rehearse-shared-gpu"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
@@ -280,7 +356,7 @@ def test_bench_extra_window_two_ranks(tmp_path):
     """N = 2: rank 0 runs the extra-window child job (itself two ranks) while rank 1 waits on the
     store; the record carries it and the job exits cleanly."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--extra-windows", "on",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--extra-windows", "on",
                         "--extra-steps", "2", "--stock-baseline", "off", *TINY], cwd=tmp_path, capture_output=True,
                        text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -296,7 +372,7 @@ def test_bench_extra_window_record(tmp_path):
     """--extra-windows on: the fp32 child job runs after the headline and lands under
     extra_windows, outside the headline fields."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--extra-windows", "on",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--extra-windows", "on",
                         "--extra-steps", "2", "--stock-baseline", "off", *TINY], cwd=tmp_path, capture_output=True,
                        text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -337,7 +413,7 @@ def test_bench_deadline_survives_hung_child_jobs(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(DPT_TEST_HANG_CHILD="1", DPT_TEST_TAG=tag)
     t0 = time.time()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stock-baseline", "on",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--stock-baseline", "on",
                         "--extra-windows", "on", "--extra-steps", "2", "--deadline", "90", *TINY],
                        cwd=tmp_path, capture_output=True, text=True, timeout=600, env=env)
     wall = time.time() - t0
@@ -372,7 +448,7 @@ def test_bench_sigterm_during_child_jobs_still_prints_the_record(tmp_path):
     tag = uuid.uuid4().hex
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(DPT_TEST_HANG_CHILD="1", DPT_TEST_TAG=tag)
-    p = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stock-baseline", "on",
+    p = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--stock-baseline", "on",
                           "--deadline", "600", *TINY], cwd=tmp_path, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, text=True, env=env)
     t0 = time.time()

@@ -12,7 +12,7 @@ on by default (launch-bound step).  Two checks (bench/graph_parity.py):
   work would be off by ~1);
 * free-running: 300 steps replayed vs 300 eager from the same init on the learnable synthetic
   task (class prototypes + fresh noise, ``--synthetic-task prototypes``); the windowed loss curves
-  must stay within a band after the first 150 steps (the lr 0.1 transient, only bounded) and both
+  (window medians) must stay within a band after the first 150 steps (the lr 0.1 transient, only bounded) and both
   runs must learn the task.  (On the default 4-batch random-label pool the run is a memorisation
   race whose speed differs between two EAGER runs of this configuration by as much as between
   replay and eager - MIOpen's find-mode algorithms are not deterministic - so that task cannot
@@ -70,9 +70,16 @@ def test_replayed_run_tracks_eager_run(benchmark_mode):
         a = sum(g[i:i + w]) / w
         b = sum(e[i:i + w]) / w
         assert a < 1.0 and b < 1.0, (i, a, b)
-    # settled: the two runs learn the task to the same loss
+    # settled: the two runs learn the task to the same loss.  At lr 0.1 without decay either run can
+    # still throw a short loss spike here (an EAGER run's 25-step means went 0.023 -> 0.27 -> 0.067 ->
+    # 0.14 -> 0.047 over steps 150-249 of a clean-checkout suite run while the replayed run stayed at
+    # 0.022; the per-step agreement of replay and eager is the teacher-forced test's job), and one
+    # spike moves a 50-step mean by more than the band.  So the band is held on the window's MEDIAN,
+    # which a spike of under 25 steps cannot move, and the mean is held to the transient's bound.
+    import statistics
     for i in range(150, 300, w):
-        a = sum(g[i:i + w]) / w
-        b = sum(e[i:i + w]) / w
+        a = statistics.median(g[i:i + w])
+        b = statistics.median(e[i:i + w])
         assert abs(a - b) <= 0.1 * max(b, 0.5) + 0.05, (i, a, b)
+        assert sum(g[i:i + w]) / w < 1.0 and sum(e[i:i + w]) / w < 1.0, i
     assert sum(g[-w:]) / w < 0.2 and sum(e[-w:]) / w < 0.2
