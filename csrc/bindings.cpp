@@ -589,7 +589,7 @@ void check_cl_f32(const Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), name, ": expected channels_last memory");
 }
 
-Tensor conv_f32_fwd(Tensor x, Tensor w, int64_t stride, int64_t pad) {
+Tensor conv_f32_fwd(Tensor x, Tensor w, int64_t stride, int64_t pad, bool split) {
   check_cl_f32(x, "x");
   check_cl_f32(w, "w");
   const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
@@ -605,13 +605,13 @@ Tensor conv_f32_fwd(Tensor x, Tensor w, int64_t stride, int64_t pad) {
   Tensor ws = wsn > 0 ? at::empty({wsn}, x.options()) : Tensor();
   dpt::launch_conv_f32(x.data_ptr<float>(), w.data_ptr<float>(), y.data_ptr<float>(),
                        ws.defined() ? ws.data_ptr<float>() : nullptr, false, N, H, W, C, Ho, Wo, Co, R, S,
-                       (int)stride, (int)pad, cur_stream(x));
+                       (int)stride, (int)pad, cur_stream(x), split);
   return y;
 }
 
 // dx of a conv with input H x W: the transposed-conv gather of dy against the weight
 // transposed to [C][R][S][Co] (a copy of the small weight tensor).
-Tensor conv_f32_dgrad(Tensor dy, Tensor w, int64_t stride, int64_t pad, int64_t H, int64_t W) {
+Tensor conv_f32_dgrad(Tensor dy, Tensor w, int64_t stride, int64_t pad, int64_t H, int64_t W, bool split) {
   check_cl_f32(dy, "grad_output");
   check_cl_f32(w, "w");
   const int N = dy.size(0), Co = dy.size(1), Ho = dy.size(2), Wo = dy.size(3);
@@ -627,11 +627,11 @@ Tensor conv_f32_dgrad(Tensor dy, Tensor w, int64_t stride, int64_t pad, int64_t 
   Tensor ws = wsn > 0 ? at::empty({wsn}, dy.options()) : Tensor();
   dpt::launch_conv_f32(dy.data_ptr<float>(), wt.data_ptr<float>(), dx.data_ptr<float>(),
                        ws.defined() ? ws.data_ptr<float>() : nullptr, true, N, (int)H, (int)W, C, Ho, Wo, Co, R, S,
-                       (int)stride, (int)pad, cur_stream(dy));
+                       (int)stride, (int)pad, cur_stream(dy), split);
   return dx;
 }
 
-Tensor conv_f32_wgrad(Tensor dy, Tensor x, std::vector<int64_t> wshape, int64_t stride, int64_t pad) {
+Tensor conv_f32_wgrad(Tensor dy, Tensor x, std::vector<int64_t> wshape, int64_t stride, int64_t pad, bool split) {
   check_cl_f32(dy, "grad_output");
   check_cl_f32(x, "x");
   TORCH_CHECK(wshape.size() == 4, "conv_f32_wgrad: weight shape must be [Co, C, R, S]");
@@ -647,7 +647,7 @@ Tensor conv_f32_wgrad(Tensor dy, Tensor x, std::vector<int64_t> wshape, int64_t 
   Tensor ws = wsn > 0 ? at::empty({wsn}, x.options()) : Tensor();
   dpt::launch_conv_f32_wgrad(dy.data_ptr<float>(), x.data_ptr<float>(), dw.data_ptr<float>(),
                              ws.defined() ? ws.data_ptr<float>() : nullptr, N, H, W, C, Ho, Wo, Co, R, S,
-                             (int)stride, (int)pad, cur_stream(x));
+                             (int)stride, (int)pad, cur_stream(x), split);
   return dw;
 }
 
@@ -1268,11 +1268,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("space_to_depth2", &space_to_depth2, py::arg("x"), py::arg("out_f16") = false);
   m.def("conv_wgrad", &conv_wgrad, py::arg("grad_output"), py::arg("x"), py::arg("weight_shape"), py::arg("stride"),
         py::arg("pad"), py::arg("fp32_out"), py::arg("target_blocks") = 0);
-  m.def("conv_f32_fwd", &conv_f32_fwd, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad"));
+  m.def("conv_f32_fwd", &conv_f32_fwd, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad"),
+        py::arg("split") = false);  // split: the split-bf16 mode (conv_f32_kernels.hip header)
   m.def("conv_f32_dgrad", &conv_f32_dgrad, py::arg("grad_output"), py::arg("w"), py::arg("stride"), py::arg("pad"),
-        py::arg("H"), py::arg("W"));
+        py::arg("H"), py::arg("W"), py::arg("split") = false);
   m.def("conv_f32_wgrad", &conv_f32_wgrad, py::arg("grad_output"), py::arg("x"), py::arg("weight_shape"),
-        py::arg("stride"), py::arg("pad"));
+        py::arg("stride"), py::arg("pad"), py::arg("split") = false);
   m.def("im2col", &im2col, py::arg("x"), py::arg("R"), py::arg("S"), py::arg("stride"), py::arg("pad"), py::arg("Kp"));
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("heads"), py::arg("scale"));
   m.def("attn_set_bwd_split", &dpt::attn_set_bwd_split, py::arg("on"));

@@ -26,11 +26,30 @@
 // fp32 K-step is 64 MFMAs x 64 cycles per wave, so 8 B/clk/CU of operand traffic suffices).
 // Split-K over blocks when the tile grid is small; the partial tiles are reduced by
 // conv_f32_reduce_kernel (fixed summation order).
+//
+// Split-bf16 mode (SPLIT = true; the role TF32 plays on hardware that has it - gfx950 has no xf32).
+// Numerics contract, for the forward, the input gradient (operands dy and w) and the weight
+// gradient (operands dy and x) alike:
+//   every fp32 operand element v becomes  hi = bf16_rne(v),  lo = bf16_rne(v - float(hi))
+//   (both rounded to nearest even by v_cvt_pk_bf16_f32; the subtraction is exact in fp32), and
+//   each product a*b is computed as  a_hi*b_hi + a_hi*b_lo + a_lo*b_hi  (lo*lo is dropped) by
+//   three v_mfma_f32_32x32x16_bf16 into the same fp32 accumulator: ~4.5e-6 relative L2 against
+//   fp64, between TF32 (3e-4) and exact fp32 (2e-7).
+// Order: a K-step of 32 is two K groups of 16, taken in order; within a group every accumulator
+// tile receives hi*hi, then hi*lo, then lo*hi.  Group g takes, from lane (lr, lh), the 8 floats
+// 16g + 8lh .. + 7 of its LDS row (forward / dgrad) or the 8 pixel rows 16g + 8lh + j of its
+// column (wgrad) - the bf16 MFMA's operand map, the same K order for A and B.
+// Staging, swizzle, zero padding (0 splits to hi = lo = 0), XCD remap, epilogue and the split-K
+// reduce are the exact mode's, so the mode is bitwise deterministic and replay-safe too.
+// Non-finite and large inputs: an inf gives hi = inf, lo = bf16(inf - inf) = NaN, so the outputs
+// that depend on it are non-finite but may be NaN where exact fp32 gives inf; a finite |v| above
+// the largest bf16 (~3.39e38) rounds hi to inf with the same effect.  Neither is worked around.
 #include <algorithm>
 #include <stdexcept>
 
 #include "common.h"
 #include "kernels.h"
+#include "mfma.h"
 
 namespace dpt {
 namespace cf32 {
@@ -52,6 +71,39 @@ __device__ __forceinline__ void glds16(const __amdgpu_buffer_rsrc_t& rs, unsigne
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_base, 16, off, 0, 0, 0);
 }
 
+// split-bf16 operand fragments of 8 fp32 values: hi = bf16_rne(v), lo = bf16_rne(v - float(hi))
+__device__ __forceinline__ void split8(const float (&v)[8], bf16x8_t& hi, bf16x8_t& lo) {
+#pragma unroll
+  for (int j = 0; j < 8; j += 2) {
+    const f32x2_t f = {v[j], v[j + 1]};
+    const bf16x2_t h = __builtin_convertvector(f, bf16x2_t);
+    const uint32_t u = __builtin_bit_cast(uint32_t, h);
+    const f32x2_t r = {v[j] - __uint_as_float(u << 16), v[j + 1] - __uint_as_float(u & 0xffff0000u)};
+    const bf16x2_t l = __builtin_convertvector(r, bf16x2_t);
+    hi[j] = h[0];
+    hi[j + 1] = h[1];
+    lo[j] = l[0];
+    lo[j + 1] = l[1];
+  }
+}
+
+// one K group of 16 in split-bf16 mode: hi*hi, then hi*lo, then lo*hi into every accumulator tile
+__device__ __forceinline__ void split_mfma(f32x16 (&acc)[2][2], const bf16x8_t (&ah)[2], const bf16x8_t (&al)[2],
+                                           const bf16x8_t (&bh)[2], const bf16x8_t (&bl)[2]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+}
+
 }  // namespace cf32
 
 struct ConvF32Args {
@@ -68,7 +120,8 @@ struct ConvF32Args {
 };
 
 // DGRAD = false: forward; true: backward-data (transposed-conv gather of dy).
-template <bool DGRAD>
+// SPLIT = false: exact fp32 MFMAs; true: the split-bf16 contract of the header.
+template <bool DGRAD, bool SPLIT>
 __global__ __launch_bounds__(cf32::kThreads, 2) void conv_f32_mk_kernel(ConvF32Args p) {
   using namespace cf32;
   constexpr int STAGE = (BM + BN) * kRowBytes;  // 32 KiB
@@ -207,6 +260,30 @@ __global__ __launch_bounds__(cf32::kThreads, 2) void conv_f32_mk_kernel(ConvF32A
     __syncthreads();
     const unsigned char* a = lds;
     const unsigned char* b = lds + BM * kRowBytes;
+    if constexpr (SPLIT) {
+      // K group g: lane (lr, lh) supplies K indices 16g + 8lh + 0..7 = chunks 4g + 2lh, 4g + 2lh + 1
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        bf16x8_t ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int row = wm * 64 + i * 32 + lr;
+          const float4 u = *reinterpret_cast<const float4*>(a + row * kRowBytes + cf32::swz(row, 4 * g + 2 * lh) * 16);
+          const float4 v = *reinterpret_cast<const float4*>(a + row * kRowBytes + cf32::swz(row, 4 * g + 2 * lh + 1) * 16);
+          const float f[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
+          split8(f, ah[i], al[i]);
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int row = wn * 64 + j * 32 + lr;
+          const float4 u = *reinterpret_cast<const float4*>(b + row * kRowBytes + cf32::swz(row, 4 * g + 2 * lh) * 16);
+          const float4 v = *reinterpret_cast<const float4*>(b + row * kRowBytes + cf32::swz(row, 4 * g + 2 * lh + 1) * 16);
+          const float f[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
+          split8(f, bh[j], bl[j]);
+        }
+        split_mfma(acc, ah, al, bh, bl);
+      }
+    } else {
     // lane (lr, lh) supplies K index 16*lh + t to MFMA t: its 16 floats are chunks 4lh..4lh+3
     float4 fa[2][4], fb[2][4];
 #pragma unroll
@@ -232,6 +309,7 @@ __global__ __launch_bounds__(cf32::kThreads, 2) void conv_f32_mk_kernel(ConvF32A
 #pragma unroll
           for (int j = 0; j < 2; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][q][e], fb[j][q][e], acc[i][j], 0, 0, 0);
+    }
     __syncthreads();
   }
 
@@ -265,6 +343,9 @@ struct ConvF32WArgs {
 // dW = dy^T X over pixel K-steps of 32; both operands staged as [32 pixels][128] float images
 // (512-byte rows, two rows per 1 KiB glds instruction) and read one float per lane and MFMA
 // (ds_read_b32: 32 consecutive floats of one row per 32-lane half - conflict-free).
+// SPLIT: K group g reads the 8 pixel rows 16g + 8lh + j of the lane's column (as many ds_read_b32)
+// and packs them into the bf16 x 8 fragments of the split-bf16 contract.
+template <bool SPLIT>
 __global__ __launch_bounds__(cf32::kThreads, 2) void conv_f32_wgrad_kernel(ConvF32WArgs p) {
   using namespace cf32;
   constexpr int IMG = BK * BM * 4;  // 16 KiB per operand
@@ -345,6 +426,28 @@ __global__ __launch_bounds__(cf32::kThreads, 2) void conv_f32_wgrad_kernel(ConvF
     __syncthreads();
     const float* A = reinterpret_cast<const float*>(lds);
     const float* B = reinterpret_cast<const float*>(lds + IMG);
+    if constexpr (SPLIT) {
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        const int krow0 = 16 * g + 8 * lh;
+        bf16x8_t ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          float f[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) f[j] = A[(krow0 + j) * BM + wm * 64 + i * 32 + lr];
+          split8(f, ah[i], al[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          float f[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) f[j] = B[(krow0 + j) * BN + wn * 64 + i * 32 + lr];
+          split8(f, bh[i], bl[i]);
+        }
+        split_mfma(acc, ah, al, bh, bl);
+      }
+    } else
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
       const int krow = t + 16 * lh;
@@ -425,7 +528,7 @@ int64_t conv_f32_workspace(int64_t M, int ncols, int K, int* splits_out) {
 }
 
 void launch_conv_f32(const float* a, const float* b, float* out, float* ws, bool dgrad, int N, int H, int W, int C,
-                     int Ho, int Wo, int Co, int R, int S, int stride, int pad, hipStream_t st) {
+                     int Ho, int Wo, int Co, int R, int S, int stride, int pad, hipStream_t st, bool split) {
   ConvF32Args p{};
   p.a = a;
   p.b = b;
@@ -448,8 +551,13 @@ void launch_conv_f32(const float* a, const float* b, float* out, float* ws, bool
   if (p.splits > 1 && ws == nullptr) throw std::invalid_argument("conv_f32: split-K needs a workspace");
   p.out = p.splits > 1 ? ws : out;
   const dim3 grid(p.m_tiles * p.n_tiles * p.splits);
-  if (dgrad) conv_f32_mk_kernel<true><<<grid, cf32::kThreads, 0, st>>>(p);
-  else conv_f32_mk_kernel<false><<<grid, cf32::kThreads, 0, st>>>(p);
+  if (dgrad) {
+    if (split) conv_f32_mk_kernel<true, true><<<grid, cf32::kThreads, 0, st>>>(p);
+    else conv_f32_mk_kernel<true, false><<<grid, cf32::kThreads, 0, st>>>(p);
+  } else {
+    if (split) conv_f32_mk_kernel<false, true><<<grid, cf32::kThreads, 0, st>>>(p);
+    else conv_f32_mk_kernel<false, false><<<grid, cf32::kThreads, 0, st>>>(p);
+  }
   if (p.splits > 1) {
     const int64_t n4 = p.M * p.ncols / 4;
     conv_f32_reduce_kernel<<<grid_for(n4, 2), kBlock, 0, st>>>(reinterpret_cast<const float4*>(ws), n4, p.splits,
@@ -465,7 +573,7 @@ int64_t conv_f32_wgrad_workspace(int N, int Ho, int Wo, int Co, int J) {
 }
 
 void launch_conv_f32_wgrad(const float* dy, const float* x, float* dw, float* ws, int N, int H, int W, int C,
-                           int Ho, int Wo, int Co, int R, int S, int stride, int pad, hipStream_t st) {
+                           int Ho, int Wo, int Co, int R, int S, int stride, int pad, hipStream_t st, bool split) {
   ConvF32WArgs p{};
   p.dy = dy;
   p.x = x;
@@ -485,7 +593,8 @@ void launch_conv_f32_wgrad(const float* dy, const float* x, float* dw, float* ws
   if (p.splits > 1 && ws == nullptr) throw std::invalid_argument("conv_f32_wgrad: split-K needs a workspace");
   p.out = p.splits > 1 ? ws : dw;
   const dim3 grid(p.m_tiles * p.n_tiles * p.splits);
-  conv_f32_wgrad_kernel<<<grid, cf32::kThreads, 0, st>>>(p);
+  if (split) conv_f32_wgrad_kernel<true><<<grid, cf32::kThreads, 0, st>>>(p);
+  else conv_f32_wgrad_kernel<false><<<grid, cf32::kThreads, 0, st>>>(p);
   if (p.splits > 1) {
     const int64_t n4 = (int64_t)Co * p.J / 4;
     conv_f32_reduce_kernel<<<grid_for(n4, 2), kBlock, 0, st>>>(reinterpret_cast<const float4*>(ws), n4, p.splits,

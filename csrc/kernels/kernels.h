@@ -300,10 +300,14 @@ void launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* d
 // deterministic split-K).  dgrad = true: a is dy [N,Ho,Wo,Co], b the transposed weight
 // [C][R][S][Co], out dx [N,H,W,C]; otherwise a is x, b the weight [Co][R][S][C], out y.
 // ws: conv_f32_workspace(...) floats when that is > 0 (split-K partial tiles).
+// split = true: the split-bf16 mode - every fp32 operand element as hi + lo bf16 (both rounded to
+// nearest even), three v_mfma_f32_32x32x16_bf16 per K group of 16 (hi*hi, hi*lo, lo*hi) into the
+// same fp32 accumulators; same tiling, workspace, split-K reduce and shape checks as exact mode.
 int64_t conv_f32_workspace(int64_t M, int ncols, int K, int* splits = nullptr);
 void launch_conv_f32(const float* a, const float* b, float* out, float* ws, bool dgrad, int N, int H, int W, int C,
-                     int Ho, int Wo, int Co, int R, int S, int stride, int pad, hipStream_t st);
+                     int Ho, int Wo, int Co, int R, int S, int stride, int pad, hipStream_t st, bool split = false);
 int64_t conv_f32_wgrad_workspace(int N, int Ho, int Wo, int Co, int J);
 void launch_conv_f32_wgrad(const float* dy, const float* x, float* dw, float* ws, int N, int H, int W, int C,
-                           int Ho, int Wo, int Co, int R, int S, int stride, int pad, hipStream_t st);
+                           int Ho, int Wo, int Co, int R, int S, int stride, int pad, hipStream_t st,
+                           bool split = false);
 }  // namespace dpt

@@ -100,6 +100,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="native impl, fp32 (no --amp): run the convolutions on the hand-written fp32 MFMA "
                         "kernels (exact, bitwise deterministic, replay-safe) instead of MIOpen (faster on "
                         "ResNet-50: profiles/conv_f32_r5.md)")
+    g.add_argument("--fp32-conv", choices=("miopen", "exact", "split-bf16"), default=None,
+                   help="native impl, fp32 (no --amp): which convolution path this model takes.  miopen: MIOpen, "
+                        "even with DPT_NATIVE_CONV_F32=1; exact: the fp32 MFMA kernels, the same as "
+                        "--native-conv-fp32; split-bf16: the same kernels on the bf16 matrix cores - every fp32 "
+                        "operand as a sum of two bf16 numbers, three MFMAs per product, fp32 accumulation: about "
+                        "4e-6 relative error, between TF32 (3e-4) and fp32 (2e-7), bitwise deterministic and "
+                        "replay-safe (profiles/conv_f32_split.md).  Default: MIOpen unless --native-conv-fp32 "
+                        "or DPT_NATIVE_CONV_F32=1")
     g.add_argument("--conv-streamk", choices=("off", "auto", "all"),
                    default=os.environ.get("DPT_CONV_STREAMK", "off"),
                    help="native impl: stream-K grids for the MFMA convs whose tiles spread unevenly over the "
@@ -168,8 +176,24 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.native_conv_fp32 and args.fp32_conv in ("miopen", "split-bf16"):
+        parser.error(f"--native-conv-fp32 selects the exact fp32 MFMA kernels and contradicts --fp32-conv {args.fp32_conv}")
     return finalize(args)
+
+
+def fp32_conv_routing(args: argparse.Namespace):
+    """(native_f32, f32_mode) of ``--fp32-conv`` / ``--native-conv-fp32`` for models/layers.py
+    ``set_conv_routing``: whether this model's fp32 convs take the MFMA kernels (None: the process
+    default DPT_NATIVE_CONV_F32) and in which arithmetic (None: the process default
+    DPT_CONV_F32_MODE)."""
+    choice = getattr(args, "fp32_conv", None)
+    if choice == "miopen":
+        return False, None
+    if choice in ("exact", "split-bf16"):
+        return True, choice
+    return (True if getattr(args, "native_conv_fp32", False) else None), None
 
 
 def finalize(args: argparse.Namespace) -> argparse.Namespace:

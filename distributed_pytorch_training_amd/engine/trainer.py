@@ -109,21 +109,25 @@ class Trainer:
         # conv_kernels.hip), which made the MFMA path faster than MIOpen on ResNet-18 / 32x32
         # under hipGraph too; DPT_CONV_MIN_PIXELS still routes tiny convs to MIOpen
         min_px = None
-        # --native-conv-fp32: this model's fp32 convs on the fp32 MFMA kernels (routing stored per
-        # conv module, never process-wide: ADVICE r5)
-        f32 = True if getattr(args, "native_conv_fp32", False) else None
+        # --native-conv-fp32 / --fp32-conv: this model's fp32 convs on the fp32 MFMA kernels, exact
+        # or split-bf16 (routing and mode stored per conv module, never process-wide: ADVICE r5)
+        from ..config import fp32_conv_routing
+        f32, f32_mode = fp32_conv_routing(args)
+        flag = "--native-conv-fp32" if getattr(args, "native_conv_fp32", False) else \
+            f"--fp32-conv {getattr(args, 'fp32_conv', None)}"
         if f32 and not use_native_conv:
             import warnings
-            warnings.warn("--native-conv-fp32 has no effect: the MFMA conv kernels need a GPU, channels_last "
+            warnings.warn(f"{flag} has no effect: the MFMA conv kernels need a GPU, channels_last "
                           "activations and native convs (no --no-native-conv)")
         if f32 and self.amp:
             import warnings
-            warnings.warn("--native-conv-fp32 only affects fp32 convolutions; under --amp the 16-bit MFMA "
+            warnings.warn(f"{flag} only affects fp32 convolutions; under --amp the 16-bit MFMA "
                           "kernels run")
         if getattr(args, "fused_bn", True) and gpu_cl:
-            fuse_native_layers(model, native_conv=use_native_conv, min_pixels=min_px, native_f32=f32)
+            fuse_native_layers(model, native_conv=use_native_conv, min_pixels=min_px, native_f32=f32,
+                               f32_mode=f32_mode)
         else:
-            set_conv_routing(model, use_native_conv, min_px, f32)
+            set_conv_routing(model, use_native_conv, min_px, f32, f32_mode)
         # per-step flip cache of the stride-1 backward-data weights (ops/conv.py)
         self._native_conv_cache = use_native_conv
         params_in_order = [p for p in model.parameters() if p.requires_grad]

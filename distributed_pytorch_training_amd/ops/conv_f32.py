@@ -33,6 +33,12 @@ ENABLED = os.environ.get("DPT_NATIVE_CONV_F32", "0") == "1"
 # Which convs the enabled path takes (A/B, DPT_NATIVE_CONV_F32_SCOPE): "all", "1x1" (one-tap,
 # stride 1), "1x1s" (one-tap, any stride), "kxk" (multi-tap convs only); the rest stay on MIOpen.
 SCOPE = os.environ.get("DPT_NATIVE_CONV_F32_SCOPE", "all")
+# Arithmetic of the enabled path (A/B, DPT_CONV_F32_MODE; per model: ``--fp32-conv``): "exact" fp32
+# MFMAs, or "split-bf16" - three bf16 MFMAs per product group, ~4.5e-6 relative (``conv2d``).
+# Measured on ResNet-50 / 224 / batch 256: 65.3 ms/step against 80.0 ms on MIOpen and 106.8 ms in
+# exact mode; on ResNet-18 / 32x32 shapes MIOpen stays ahead (profiles/conv_f32_split.md).  Opt-in.
+MODES = ("exact", "split-bf16")
+MODE = os.environ.get("DPT_CONV_F32_MODE", "exact")
 _CL = torch.channels_last
 
 
@@ -87,13 +93,52 @@ class _ConvF32(torch.autograd.Function):
         return dx, dw, None, None
 
 
-def conv2d(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
-    """y = conv2d(x, w, stride, pad), fp32, channels_last, on the fp32 MFMA kernels."""
+class _ConvF32Split(torch.autograd.Function):
+    """The split-bf16 mode: the same three kernels with ``split=True``; its own Function, so the
+    exact mode's Function and its call are untouched."""
+
+    @staticmethod
+    def forward(ctx, x, w, stride: int, pad: int):
+        ctx.save_for_backward(x, w)
+        ctx.stride, ctx.pad = stride, pad
+        return native().conv_f32_fwd(x, w, stride, pad, split=True)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = _cl(dy.float())
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = native().conv_f32_dgrad(dy, w, ctx.stride, ctx.pad, x.shape[2], x.shape[3], split=True)
+        if ctx.needs_input_grad[1]:
+            dw = native().conv_f32_wgrad(dy, x, list(w.shape), ctx.stride, ctx.pad, split=True)
+        return dx, dw, None, None
+
+
+def conv2d(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, mode: str = "exact") -> torch.Tensor:
+    """y = conv2d(x, w, stride, pad), fp32, channels_last, on the MFMA kernels.
+
+    ``mode="exact"``: fp32 MFMAs, one rounding per product (2e-7 relative L2 against fp64).
+
+    ``mode="split-bf16"``: every fp32 operand element ``v`` becomes ``hi = bf16_rne(v)`` and
+    ``lo = bf16_rne(v - float(hi))`` (round to nearest even; the subtraction is exact), and each
+    product is ``a_hi*b_hi + a_hi*b_lo + a_lo*b_hi`` (``lo*lo`` dropped): three bf16 MFMAs per K
+    group of 16, in that order, into the same fp32 accumulator.  The forward splits x and w, the
+    input gradient dy and w, the weight gradient dy and x.  About 4.5e-6 relative L2 against fp64
+    - between TF32 (3e-4) and exact fp32 - and, like exact mode, bitwise deterministic and
+    replay-safe (``ops/reference.py`` ``conv2d_split_bf16`` is the contract in plain torch).  An
+    ``inf`` input may come out as ``NaN`` (``lo = bf16(inf - inf)``), and a finite ``|v|`` above the
+    largest bf16 rounds ``hi`` to infinity: the outputs that depend on such an element are
+    non-finite, all others unaffected."""
+    if mode not in MODES:
+        raise ValueError(f"conv_f32.conv2d: mode must be one of {MODES}, got {mode!r}")
     cin = w.shape[1]
     if cin % 4:
         extra = 4 - cin % 4     # zero channels: the same products, autograd drops their gradients
         x = F.pad(x, (0, 0, 0, 0, 0, extra))
         w = F.pad(w, (0, 0, 0, 0, 0, extra))
+    if mode == "split-bf16":
+        return _ConvF32Split.apply(_cl(x), _cl(w), int(stride), int(pad))
     return _ConvF32.apply(_cl(x), _cl(w), int(stride), int(pad))
 
 
@@ -107,9 +152,11 @@ class NativeConv2d(nn.Conv2d):
     dpt_native_conv = True
     dpt_min_pixels = None
     dpt_native_conv_f32 = None    # per-model fp32 routing (set_conv_routing); None = ENABLED (env)
+    dpt_conv_f32_mode = None      # per-model arithmetic of that route ("exact" / "split-bf16"); None = MODE
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.dpt_native_conv and supported(x, self.weight, self.bias, self.stride, self.padding,
                                               self.dilation, self.groups, self.dpt_native_conv_f32):
-            return conv2d(x, self.weight, self.stride[0], self.padding[0])
+            mode = MODE if self.dpt_conv_f32_mode is None else self.dpt_conv_f32_mode
+            return conv2d(x, self.weight, self.stride[0], self.padding[0], mode)
         return super().forward(x)

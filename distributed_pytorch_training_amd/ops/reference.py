@@ -143,3 +143,38 @@ def unpack_bf16(src, dst, scale, host_factor, found_inf) -> None:
     dst.copy_(src.float())
     if found_inf is not None:
         grad_check(dst, scale, host_factor, found_inf)
+
+
+# ---- split-bf16 fp32 convolution (csrc/kernels/conv_f32_kernels.hip, SPLIT = true) ------------
+# The contract in plain torch: every fp32 operand element v is hi + lo with hi = bf16_rne(v) and
+# lo = bf16_rne(v - float(hi)) (the subtraction is exact in fp32), and a product a*b is
+# a_hi*b_hi + a_hi*b_lo + a_lo*b_hi (lo*lo dropped).  The three convolutions run in fp64, so what
+# is left between these functions and the kernels is the kernels' fp32 accumulation.
+def split_bf16(v: torch.Tensor):
+    """(hi, lo) of an fp32 tensor, both as fp64 tensors holding bf16 values (CPU)."""
+    v = v.detach().float().cpu()
+    hi = v.to(torch.bfloat16).float()
+    lo = (v - hi).to(torch.bfloat16).float()
+    return hi.double(), lo.double()
+
+
+def _three_terms(fn, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    ah, al = split_bf16(a)
+    bh, bl = split_bf16(b)
+    return fn(ah, bh) + fn(ah, bl) + fn(al, bh)
+
+
+@torch.no_grad()
+def conv2d_split_bf16(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
+    """y (fp64, CPU) of conv2d(x, w, stride, pad) under the split-bf16 contract (operands x, w)."""
+    return _three_terms(lambda a, b: torch.nn.functional.conv2d(a, b, stride=stride, padding=pad), x, w)
+
+
+@torch.no_grad()
+def conv2d_split_bf16_grads(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, stride: int, pad: int):
+    """(dx, dw) (fp64, CPU) of that convolution under the same contract: the input gradient splits
+    dy and w, the weight gradient splits dy and x."""
+    xs, ws = tuple(x.shape), tuple(w.shape)
+    dx = _three_terms(lambda g, b: torch.nn.grad.conv2d_input(xs, b, g, stride=stride, padding=pad), dy, w)
+    dw = _three_terms(lambda g, a: torch.nn.grad.conv2d_weight(a, ws, g, stride=stride, padding=pad), dy, x)
+    return dx, dw
