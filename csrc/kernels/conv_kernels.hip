@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <stdexcept>
+#include <type_traits>
 
 #include "carry.h"
 #include "gelu.h"
@@ -109,25 +110,25 @@ struct ConvSk {
 };
 
 struct ConvFwdArgs {
-  const uint16_t* x;  // [N, H, W, C]
-  const uint16_t* w;  // [Cout, R, S, C]
-  uint16_t* y;        // [N, Ho, Wo, Cout]
-  float* psum;        // optional BN partials [Cout][m_tiles]
-  float* psq;
-  int N, H, W, C, Ho, Wo, Cout, R, S, stride, pad;
-  int64_t M;
-  int m_tiles, n_tiles;  // m_tiles: 128-row tiles (the BN-partials layout)
-  int mt256;             // 256-row tiles when BM = 256
+  const uint16_t* x = nullptr;  // [N, H, W, C]
+  const uint16_t* w = nullptr;  // [Cout, R, S, C]
+  uint16_t* y = nullptr;        // [N, Ho, Wo, Cout]
+  float* psum = nullptr;        // optional BN partials [Cout][m_tiles]
+  float* psq = nullptr;
+  int N = 0, H = 0, W = 0, C = 0, Ho = 0, Wo = 0, Cout = 0, R = 0, S = 0, stride = 0, pad = 0;
+  int64_t M = 0;
+  int m_tiles = 0, n_tiles = 0;  // m_tiles: 128-row tiles (the BN-partials layout)
+  int mt256 = 0;         // 256-row tiles when BM = 256
   // BNB epilogue: the BatchNorm whose ReLU output was this conv's input
-  const uint16_t* bnx;   // BN input x [M, Cout] (same layout as y)
-  const float* bn_mean;  // [Cout]
-  const float* bn_coef;  // [2*Cout] = [a | b]
-  float* bp1;            // partials [Cout][m_tiles]
-  float* bp2;
+  const uint16_t* bnx = nullptr;   // BN input x [M, Cout] (same layout as y)
+  const float* bn_mean = nullptr;  // [Cout]
+  const float* bn_coef = nullptr;  // [2*Cout] = [a | b]
+  float* bp1 = nullptr;            // partials [Cout][m_tiles]
+  float* bp2 = nullptr;
   // BNR epilogue: that BatchNorm was a block tail relu(bn(x) + res) whose output also fed the
   // next block's identity path
-  const uint16_t* bny;    // its output y (ReLU mask)
-  const uint16_t* bnres;  // the identity-path gradient (added before the mask)
+  const uint16_t* bny = nullptr;    // its output y (ReLU mask)
+  const uint16_t* bnres = nullptr;  // the identity-path gradient (added before the mask)
   // the same ReLU mask as 1 bit per element, [M][Cout/8] bytes written by the tail's forward
   // apply (bn_kernels.hip): read instead of bny when set - 1/16 of y's bytes
   const uint8_t* bnmask = nullptr;
@@ -135,23 +136,23 @@ struct ConvFwdArgs {
   const uint16_t* bias16 = nullptr;
   // BNR with a downsample branch: the block's identity path was BN2(x2) (folded into the tail,
   // ops/bn.py _BN2AddReLUPair): also sum s3 = sum dz*(x2 - mean2) for that BatchNorm
-  const uint16_t* bnx2;
-  const float* bn_mean2;
-  float* bp3;
+  const uint16_t* bnx2 = nullptr;
+  const float* bn_mean2 = nullptr;
+  float* bp3 = nullptr;
   // BKN tap map: GEMM tap (r, s) reads weight tap (tr0 + trs*r, ts0 + tss*s) of the Rw x Sw
   // weight (stride-1 backward-data: the flip R-1-r; strided backward-data: one parity class)
-  int Rw, Sw, tr0, trs, ts0, tss;
+  int Rw = 0, Sw = 0, tr0 = 0, trs = 0, ts0 = 0, tss = 0;
   // REMAP epilogue: GEMM output row (n, a, b) lands on row (n*oH + 2a + oph)*oW + 2b + opw
-  int oH, oW, oph, opw;
+  int oH = 0, oW = 0, oph = 0, opw = 0;
   // BNB partials: column mt + bp_off of a [Cout][bp_ld] array (the strided backward-data's
   // parity classes write consecutive column ranges of one array)
-  int bp_ld, bp_off;
-  int f16;  // fp16 element type (bf16 otherwise)
+  int bp_ld = 0, bp_off = 0;
+  int f16 = 0;  // fp16 element type (bf16 otherwise)
   // split-K (small grids): block (tile, split) reduces K-steps [split*kps, +kps) into an fp32
   // partial tile of part [splits][M][Cout]; conv_split_epilogue_kernel sums the splits and runs
   // the epilogue (16-bit rounding, BN statistics, BNB/BNR) the unsplit kernel would have run
-  float* part;
-  int splits, kps;
+  float* part = nullptr;
+  int splits = 1, kps = 0;
   // Carried backward-weight reduce (carry.h): the last red.blocks blocks of the grid sum the
   // split-K partials of a backward-weight launched just before (the same conv's) instead of
   // computing a conv tile (AttachWgradReduce, kernels.h).  red.blocks = 0: none.
@@ -1471,20 +1472,20 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {
 }
 
 struct ConvWgradArgs {
-  const uint16_t* dy;  // [N, Ho, Wo, Cout]
-  const uint16_t* x;   // [N, H, W, C]
-  float* part;         // [splits][Cout][R*S*C]
-  int N, H, W, C, Ho, Wo, Cout, R, S, stride, pad;
-  int M;               // N*Ho*Wo (< 2^31)
-  int co_tiles, n_tiles, splits, steps_per_split;
-  FastDiv div_wo, div_howo;
-  int direct;          // 1x1, stride 1, pad 0: x row = dy row
+  const uint16_t* dy = nullptr;  // [N, Ho, Wo, Cout]
+  const uint16_t* x = nullptr;   // [N, H, W, C]
+  float* part = nullptr;         // [splits][Cout][R*S*C]
+  int N = 0, H = 0, W = 0, C = 0, Ho = 0, Wo = 0, Cout = 0, R = 0, S = 0, stride = 0, pad = 0;
+  int M = 0;           // N*Ho*Wo (< 2^31)
+  int co_tiles = 0, n_tiles = 0, splits = 1, steps_per_split = 0;
+  FastDiv div_wo{}, div_howo{};
+  int direct = 0;      // 1x1, stride 1, pad 0: x row = dy row
   // K-step advance of a lane's x row by BKP = 64 pixels, 64 = A*Ho*Wo + B*Wo + Cq (host-side):
   // wi += dw_step (wrap: -wwrap, hi += stride), hi += dh_step (wrap: -hwrap); the element
   // offset moves by dp_w / dp_wwrap / dp_h / dp_hwrap alongside (image carries folded in)
-  int dw_step, wwrap, dh_step, hwrap;
-  int dp_w, dp_wwrap, dp_h, dp_hwrap;
-  int f16;             // fp16 operands (bf16 otherwise)
+  int dw_step = 0, wwrap = 0, dh_step = 0, hwrap = 0;
+  int dp_w = 0, dp_wwrap = 0, dp_h = 0, dp_hwrap = 0;
+  int f16 = 0;         // fp16 operands (bf16 otherwise)
   // conv_wgrad_halo_kernel: padded pixel count N*H*(W+2) and divisors by W+2 and H
   int Mp = 0;
   FastDiv div_wp{}, div_h{};
@@ -2140,26 +2141,177 @@ bool conv_supported_narrow(int C, int Cout, int S) {
 int conv_m_tiles(int64_t M) { return (int)((M + conv::BM - 1) / conv::BM); }
 int conv_split_cols(int64_t M) { return (int)((M + 15) / 16); }
 
-// Kernel variant: 0 = default (1-stage + LDS epilogue), 5/6 = 256-row blocks (register / LDS
-// epilogue), 1 = 2-stage + LDS epilogue, 2 = 2-stage +
-// register epilogue, 3 = 1-stage + register epilogue, 4 = 1-stage + LDS epilogue.
-// The backward-weight kernel takes 1-2 -> 2 stages, 0/3-4 -> 1 stage.
-// conv_set_variant switches at run time (A/B tests, benchmarks; the bindings' conv_set_variant).
+// ---- run-time knobs (the bindings' conv_set_* / conv_get_*: A/B tests, benchmarks) ---------------
+// Kernel variant (conv_set_variant).  Forward and backward-data (conv_fwd_dispatch, conv_fwd_big):
+//   0       production: the 128-row 1-stage tile with the LDS epilogue (= 4; measured best at every
+//           ResNet-50 shape but two, profiles/conv_*.md), under fwd_shape_variant / conv_big_auto
+//   1 - 4   128-row tiles: 1 = 2-stage + LDS epilogue, 2 = 2-stage + register epilogue,
+//           3 = 1-stage + register epilogue, 4 = 1-stage + LDS epilogue
+//   5 - 8, 14  256-row blocks (4 row tiles per wave): 5 = register epilogue, the others LDS epilogue
+//           (7 / 8 / 14 name the BK = 32 pipelined K loops of conv_fwd_pipe_kernel, but
+//           conv_fwd_dispatch tests for the 256-row codes first)
+//   9 - 13  8-wave tiles (conv_fwd_big); as 6 where the tile's width does not divide Cout
+//   fp16 always runs 4, the weight-flipping backward-data (BKN) the 1-stage 128-row tile, and
+//   launch_conv_dgrad_bnstats takes 9, 10, 12, 13 and the 1-stage 128-row tile for every other code.
+// Backward-weight: 1 - 2 = 2 stages, 20 = 8-wave 256 x 256 tiles (bench/wgrad_variants.py; leaves
+// the other passes at 0), every other code 1 stage.
 static int g_conv_variant = 0;
-static int conv_variant() { return g_conv_variant; }
+void conv_set_variant(int v) { g_conv_variant = v; }
 // forward / backward-data tile variant: codes >= 20 select backward-weight tiles only
 static int fwd_variant() { return g_conv_variant >= 20 ? 0 : g_conv_variant; }
-void conv_set_variant(int v) { g_conv_variant = v; }
 
+// 8-wave 256-row tiles under variant 0 (conv_set_big; the shapes: conv_big_auto): 0 = off, 1 = the
+// deep reductions onto narrow outputs, 2 / 3 = the deep one-tap convs.  Off by default: in the
+// ResNet-50 training step (stats / BNB / BNR epilogues, L2 shared with the neighbouring kernels)
+// the per-shape wins did not show (11680/11521 vs 11659/11534 img/s, same-box A/B).
+static int g_conv_big = 0;
+void conv_set_big(int on) { g_conv_big = on; }
+
+// 3x3 / stride 1 / pad 1 convs (and their backward-data) take the HALO K loop (conv_fwd_kernel).
+// conv_set_halo: 0 = per-tap loop (A/B), 1 = auto (default): all three B taps per load phase
+// (HB = 3) when the tile grid is at most 512 tiles (two blocks per CU) - there the grid, not LDS,
+// limits the resident blocks and one wait per three K-steps wins (3x3 512->512 @7x7: 0.075 ->
+// 0.064 ms; a 1024-tile cut-off measured slower) - else one B tap per phase (HB = 1; HB = 3
+// everywhere lost 1.2 % in the step), 2 / 3 = force HB
+static int g_conv_halo = 1;
+void conv_set_halo(int on) { g_conv_halo = on; }
+
+// B operand straight into VGPRs (conv_fwd_kernel BREG): bit 0 = 3x3 HALO convs, bit 1 = the
+// other single-stage 128-row convs (1x1, strided, stem); conv_set_breg (A/B)
+static int g_conv_breg = 0;
+void conv_set_breg(int mode) { g_conv_breg = mode; }
+int conv_get_breg() { return g_conv_breg; }
+
+// Stream-K (conv_fwd_kernel SK).  Grids whose 128 x BN tiles do not divide evenly over the 256 CUs
+// lose the idle part of the last round: 784 tiles of a ResNet-50 layer3 1x1 conv are 3 rounds on
+// 240 CUs and 4 on 16, and the K loop is bound by each CU's L2 -> LDS bandwidth, so the step takes
+// 4 tile-times where 3.06 would do (profiles/wave_efficiency_r5.md).  Stream-K spreads the (tile,
+// K-step) iterations evenly over 256 x k blocks; a tile cut between blocks costs one fp32 partial
+// tile written and read back.
+// conv_set_streamk: 0 = off, 1 = auto (per-CU tile balance below kSkEff), 2 = every eligible grid.
+static int g_conv_sk = 0;
+static double kSkEff = 0.9;
+void conv_set_streamk(int mode, double eff) {
+  g_conv_sk = mode;
+  if (eff > 0) kSkEff = eff;
+}
+int conv_get_streamk() { return g_conv_sk; }
+
+// Split-K for small grids.  A conv whose 128 x BN tile grid is far below one block per CU
+// (ResNet-18 on 32x32 images: layer4 is 4 tiles at batch 128, each a 72-step K loop) is
+// latency-bound on the K loop: split the K-steps over blocks (fp32 partials, summed by
+// conv_split_epilogue_kernel).  Target ~2 blocks per CU, at least 2 K-steps per split.
+// conv_set_splitk: 0 = never split (A/B), 1 = auto (conv_fwd_splits_for), 2 = the in-graph policy
+// everywhere (tests that compare eager with replayed steps)
+static int g_splitk = 1;
+void conv_set_splitk(int mode) { g_splitk = mode; }
+int conv_get_splitk() { return g_splitk; }
+// Thresholds of that policy: split grids of fewer than kSplitTiles tiles (eagerly: at most
+// kSplitEager tiles with >= kSplitEagerMinK K-steps) to about kSplitTarget blocks (512 / 1024
+// targets measured -1 % / -5 %, docs/DESIGN.md §7.2).
+static int kSplitTiles = 160, kSplitEager = 32, kSplitTarget = 512, kSplitEagerMinK = 24;
+// A/B knob (bench/ab_step.py): the thresholds above; a value <= 0 keeps the current one
+void conv_set_splitk_policy(int tiles, int eager_tiles, int eager_min_k, int target) {
+  if (tiles > 0) kSplitTiles = tiles;
+  if (eager_tiles > 0) kSplitEager = eager_tiles;
+  if (eager_min_k > 0) kSplitEagerMinK = eager_min_k;
+  if (target > 0) kSplitTarget = target;
+}
+
+// Per-shape forward tile policy (variant 0 only; bits, conv_set_fwd_shape_policy):
+//   1: expanding 1x1 convs with the BN-statistics epilogue (C <= 128, Cout >= 2C) -> 256-row
+//      blocks with the LDS epilogue (variant 6): the statistics partials are summed over 256
+//      rows per block instead of 128 (64->256 @56: 0.155 -> 0.130 ms with statistics, MIOpen
+//      0.106 without; bench/conv_variant_sweep.py, profiles/conv_variant_sweep_r4.md);
+//   2: the 3x3 stride-2 256->256 conv (K = 2304, M >= 32768) -> the 8-wave 256x256 tile (variant
+//      9): 0.081 -> 0.069 ms, 1.05-1.08x MIOpen.
+//   16: the s2d stem's 4x4 conv (C = 16) on the 2-stage K loop (variant 1).
+//   4 / 8: 1x1 stride-1 convs with the statistics epilogue on grids under 1,024 tiles (the deep
+//      reducing convs at 14x14 / 7x7, latency-bound with ~3 resident blocks per CU:
+//      profiles/step_pmc_r5.md) -> the BK = 32 pipelined K loop, 2 stages (variant 14, 4 blocks
+//      per CU) / 3 stages (variant 7).
+static int g_fwd_shape_policy = 0;
+void conv_set_fwd_shape_policy(int bits) { g_fwd_shape_policy = bits; }
+
+// conv_wgrad_halo_kernel modes: 0 off, 1 / 2: 128-channel strips, 3 / 4: 64-channel strips
+// (even: double-buffered), 5 auto (default; conv_set_wgrad_halo for A/B): mode 3 for 64-channel inputs,
+// where the per-tap kernel's two-tap tiles waste 1/9 of their MFMA work on a ragged last tile
+// (64x56x56 -> 64: 0.118 -> 0.085-0.095 ms); the per-tap kernel elsewhere (the halo's W+2
+// padding costs 7-29 % more MFMA work and measured level or slower at 128-512 channels,
+// profiles/wgrad_halo_r2.md)
+static int g_wgrad_halo = 5;
+void conv_set_wgrad_halo(int on) { g_wgrad_halo = on; }
+
+// Block target of the split-K backward-weight plan.  Measured per ResNet-50 shape at batch 256
+// (bench/wgrad_target_sweep.py, profiles/wgrad_target_sweep_r3.md): 1x1 / stride-1 convs (one
+// tap, streaming both operands once) want ~512 blocks - fewer fp32 partial tiles to write and
+// reduce; convs with taps or a stride want more blocks to hide their K loop, 768 on the long
+// (>= 3136 K-step) reductions and 640 on the shorter ones.  Step total 3.65 -> 3.49 ms.
+// conv_set_wgrad_target(n > 0): n blocks for every shape (the sweep); 0: this policy.
+static int g_wgrad_target = 0;
+void conv_set_wgrad_target(int blocks) { g_wgrad_target = blocks; }
+
+// backward-weight K loop depth (A/B, conv_set_wgrad_stages): 0 = the single-stage tile (4 blocks
+// per CU); 1 = the double-buffered tile (2 blocks per CU) for grids of at most one wave at 2
+// blocks per CU - there residency is set by the grid, not by LDS, so the deeper pipeline costs
+// no resident block; 2 = double-buffered everywhere
+static int g_wgrad_stages = 0;
+void conv_set_wgrad_stages(int mode) { g_wgrad_stages = mode; }
+
+// ---- kernel options by name ------------------------------------------------------------------------
+// The launch code names a kernel's boolean template parameters with these flags, OR-ed into one
+// unsigned template argument; the four launch_*_kernel templates below are the only place that
+// knows their positions.  kF16 / kDir also select conv_wgrad_kernel's F16 / DIR.
+enum : unsigned {
+  kLdsEpi = 1u << 0, kBkn = 1u << 1, kStats = 1u << 2, kBnb = 1u << 3, kBnr = 1u << 4, kRemap = 1u << 5,
+  kZsib = 1u << 6, kBnr2 = 1u << 7, kF16 = 1u << 8, kSplit = 1u << 9, kHalo = 1u << 10, kSk = 1u << 11,
+  kDgelu = 1u << 12, kBreg = 1u << 13, kDir = 1u << 14,
+};
+static constexpr bool has(unsigned flags, unsigned f) { return (flags & f) != 0; }
+static constexpr unsigned opt(bool on, unsigned f) { return on ? f : 0u; }
+// A set of flags as a value, for generic lambdas that take their epilogue at compile time.
+template <unsigned F>
+using Opts = std::integral_constant<unsigned, F>;
+
+// A run-time bool as a compile-time constant: fn(std::true_type{}) or fn(std::false_type{}).  Both
+// sides are instantiated - only for choices whose both kernels exist.
+template <class Fn>
+static void with_bool(bool b, Fn&& fn) {
+  if (b) fn(std::true_type{});
+  else fn(std::false_type{});
+}
+
+template <int BMT, int BN, int STAGES, unsigned F, int NT = conv::kThreads, int HB = 1>
+static void launch_fwd_kernel(dim3 grid, hipStream_t s, const ConvFwdArgs& a) {
+  hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, STAGES, has(F, kLdsEpi), has(F, kBkn), has(F, kStats), has(F, kBnb),
+                                      has(F, kBnr), has(F, kRemap), has(F, kZsib), has(F, kBnr2), has(F, kF16), NT,
+                                      has(F, kSplit), has(F, kHalo), HB, has(F, kSk), has(F, kDgelu), has(F, kBreg)>),
+                     grid, dim3(NT), 0, s, a);
+}
+
+template <unsigned F>
+static void launch_split_epilogue_kernel(dim3 grid, hipStream_t s, const ConvFwdArgs& a) {
+  hipLaunchKernelGGL((conv_split_epilogue_kernel<has(F, kStats), has(F, kBnb), has(F, kBnr), has(F, kBnr2),
+                                                 has(F, kRemap), has(F, kZsib), has(F, kF16)>),
+                     grid, dim3(256), 0, s, a);
+}
+
+template <int BMW, int BNW, int STAGES, unsigned F, int NT = conv::kThreads>
+static void launch_wgrad_kernel(dim3 grid, hipStream_t s, const ConvWgradArgs& a) {
+  hipLaunchKernelGGL((conv_wgrad_kernel<BMW, BNW, STAGES, has(F, kF16), NT, has(F, kDir)>), grid, dim3(NT), 0, s, a);
+}
+
+template <int BNW, int STAGES, unsigned F>
+static void launch_wgrad_halo_kernel(dim3 grid, hipStream_t s, const ConvWgradArgs& a) {
+  hipLaunchKernelGGL((conv_wgrad_halo_kernel<BNW, STAGES, has(F, kF16)>), grid, dim3(conv::kThreads), 0, s, a);
+}
+
+// ---- forward / backward-data launches ---------------------------------------------------------------
 // Production choice of the 8-wave 256-row tiles (variant 0): deep reductions onto narrow
 // outputs, where the 128 x 128 tile re-reads A from L2 once per 128 output channels and the
 // per-CU L2 -> LDS rate caps it (profiles/conv_variants_*.md, ResNet-50 batch 256):
 //   N = 256, K >= 1024, M >= 32768          -> 9  (256 x 256): 3x3 256->256 @14x14 709 -> 896 TF
 //   N = 512, K >= 2048, M <= 16384          -> 10 (256 x 128): 3x3 512->512 @7x7 714 -> 802 TF
-// Off by default: in the ResNet-50 training step (stats / BNB / BNR epilogues, L2 shared with
-// the neighbouring kernels) the per-shape wins did not show (11680/11521 vs 11659/11534 img/s,
-// same-box A/B).  conv_set_big(1) turns it on.
-static int g_conv_big = 0;
 // conv_set_big(2 / 3): the deep one-tap convs (K >= 1024 / >= 512, N a multiple of 256) on the
 // 8-wave 128 x 256 tile with the 3-stage pipelined K loop (variant 13): their grids are 392-784
 // 128 x 128 tiles of 16-32 K-steps, latency-bound at ~3 resident blocks per CU
@@ -2174,11 +2326,7 @@ static int conv_big_auto(int64_t M, int N, int64_t K, int taps) {
   if (N == 512 && K >= 2048 && M <= 16384) return 10;
   return 0;
 }
-void conv_set_big(int on) { g_conv_big = on; }
 
-
-// Launch one conv_fwd_kernel instantiation in the element type of a.f16 (fp16 is instantiated
-// for the production 128-row, 1-stage, LDS-epilogue variants only).
 // conv_fwd_kernel addresses both operands with 32-bit byte offsets through buffer descriptors
 // (num_records < 2^32, padding reads at offset 0xFFFFFF00).
 static void conv_check_offsets(const ConvFwdArgs& a, bool bkn) {
@@ -2230,20 +2378,7 @@ int take_attached_reduce(ReduceCarry& rc) {
   rc.blocks = (int)((r->n4 + kBlock / rc.ph - 1) / (kBlock / rc.ph));
   return rc.blocks;
 }
-static int take_attached_reduce(ConvFwdArgs& a) { return take_attached_reduce(a.red); }
 
-// 3x3 / stride 1 / pad 1 convs (and their backward-data) take the HALO K loop (conv_fwd_kernel).
-// conv_set_halo: 0 = per-tap loop (A/B), 1 = auto (default): all three B taps per load phase
-// (HB = 3) when the tile grid is at most 512 tiles (two blocks per CU) - there the grid, not LDS,
-// limits the resident blocks and one wait per three K-steps wins (3x3 512->512 @7x7: 0.075 ->
-// 0.064 ms; a 1024-tile cut-off measured slower) - else one B tap per phase (HB = 1; HB = 3
-// everywhere lost 1.2 % in the step), 2 / 3 = force HB
-static int g_conv_halo = 1;
-// B operand straight into VGPRs (conv_fwd_kernel BREG): bit 0 = 3x3 HALO convs, bit 1 = the
-// other single-stage 128-row convs (1x1, strided, stem); conv_set_breg (A/B)
-static int g_conv_breg = 0;
-void conv_set_breg(int mode) { g_conv_breg = mode; }
-int conv_get_breg() { return g_conv_breg; }
 static int halo_hb(const ConvFwdArgs& a, int bn) {
   if (g_conv_halo == 2) return 1;
   if (g_conv_halo == 3) return 3;
@@ -2253,22 +2388,6 @@ static bool halo_ok(const ConvFwdArgs& a) {
   return g_conv_halo && a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 && a.C % 64 == 0 && a.Ho == a.H &&
          a.Wo == a.W;
 }
-void conv_set_halo(int on) { g_conv_halo = on; }
-
-// ---- stream-K (conv_fwd_kernel<..., SK = true>) --------------------------------------------------
-// Grids whose 128 x BN tiles do not divide evenly over the 256 CUs lose the idle part of the last
-// round: 784 tiles of a ResNet-50 layer3 1x1 conv are 3 rounds on 240 CUs and 4 on 16, and the K loop
-// is bound by each CU's L2 -> LDS bandwidth, so the step takes 4 tile-times where 3.06 would do
-// (profiles/wave_efficiency_r5.md).  Stream-K spreads the (tile, K-step) iterations evenly over
-// 256 x k blocks; a tile cut between blocks costs one fp32 partial tile written and read back.
-// conv_set_streamk: 0 = off, 1 = auto (per-CU tile balance below kSkEff), 2 = every eligible grid.
-static int g_conv_sk = 0;
-static double kSkEff = 0.9;
-void conv_set_streamk(int mode, double eff) {
-  g_conv_sk = mode;
-  if (eff > 0) kSkEff = eff;
-}
-int conv_get_streamk() { return g_conv_sk; }
 
 namespace {
 struct SkWorkspace {
@@ -2337,56 +2456,38 @@ int conv_sk_blocks(int64_t tiles, int nk, int bn, int mode) {
   return G;
 }
 
-template <int BMT, int BN, int STAGES, bool LDSEPI, bool BKN, bool STATS = true, bool BNB = false,
-          bool BNR = false, bool REMAP = false, bool ZSIB = false, bool BNR2 = false, int NT = conv::kThreads>
-static void fwd_launch(dim3 grid, dim3 /*block*/, hipStream_t s, const ConvFwdArgs& a0) {
-  const dim3 block(NT);
+// Launch the BMT x BN tile with epilogue F in the element type of a.f16.  The production tile (128
+// rows, 1 stage, LDS epilogue, 4 waves) is the one with fp16, HALO, BREG and stream-K kernels;
+// a 4-wave launch also takes an attached backward-weight reduce into its grid.
+template <int BMT, int BN, int STAGES, unsigned F, int NT = conv::kThreads>
+static void fwd_launch(dim3 grid, hipStream_t s, const ConvFwdArgs& a0) {
+  constexpr bool kProd = BMT == 128 && STAGES == 1 && has(F, kLdsEpi) && NT == conv::kThreads;
   ConvFwdArgs a = a0;
-  if constexpr (NT == conv::kThreads) grid.x += (unsigned)take_attached_reduce(a);
-  conv_check_offsets(a, BKN);
-  if constexpr (BMT == 128 && STAGES == 1 && LDSEPI && !BKN && !REMAP && NT == conv::kThreads) {
-    // B operand in registers (conv_set_breg: bit 0 the 3x3 HALO convs, bit 1 the others)
+  if constexpr (NT == conv::kThreads) grid.x += (unsigned)take_attached_reduce(a.red);
+  conv_check_offsets(a, has(F, kBkn));
+  if constexpr (kProd && !has(F, kBkn | kRemap)) {
     const bool halo = halo_ok(a);
+    // B operand in registers (conv_set_breg: bit 0 the 3x3 HALO convs, bit 1 the others)
     if ((g_conv_breg & (halo ? 1 : 2)) && a.n_tiles * BN == a.Cout) {
-      if (halo) {
-        if (a.f16)
-          hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, 1, true, false, STATS, BNB, BNR, false, ZSIB, BNR2, true,
-                                              conv::kThreads, false, true, 1, false, false, true>), grid, block, 0, s, a);
-        else
-          hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, 1, true, false, STATS, BNB, BNR, false, ZSIB, BNR2, false,
-                                              conv::kThreads, false, true, 1, false, false, true>), grid, block, 0, s, a);
-      } else {
-        if (a.f16)
-          hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, 1, true, false, STATS, BNB, BNR, false, ZSIB, BNR2, true,
-                                              conv::kThreads, false, false, 1, false, false, true>), grid, block, 0, s, a);
-        else
-          hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, 1, true, false, STATS, BNB, BNR, false, ZSIB, BNR2, false,
-                                              conv::kThreads, false, false, 1, false, false, true>), grid, block, 0, s, a);
-      }
+      with_bool(a.f16, [&](auto f16) {
+        with_bool(halo, [&](auto h) {
+          launch_fwd_kernel<BMT, BN, 1, F | kBreg | opt(h.value, kHalo) | opt(f16.value, kF16)>(grid, s, a);
+        });
+      });
       return;
     }
-    if (halo) {
-      if (halo_hb(a, BN) == 3) {  // all three B taps with the halo strip
-        if (a.f16)
-          hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, 1, true, false, STATS, BNB, BNR, false, ZSIB, BNR2, true,
-                                              conv::kThreads, false, true, 3>), grid, block, 0, s, a);
-        else
-          hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, 1, true, false, STATS, BNB, BNR, false, ZSIB, BNR2, false,
-                                              conv::kThreads, false, true, 3>), grid, block, 0, s, a);
-        return;
-      }
-      if (a.f16)
-        hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, 1, true, false, STATS, BNB, BNR, false, ZSIB, BNR2, true,
-                                            conv::kThreads, false, true>), grid, block, 0, s, a);
-      else
-        hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, 1, true, false, STATS, BNB, BNR, false, ZSIB, BNR2, false,
-                                            conv::kThreads, false, true>), grid, block, 0, s, a);
+    if (halo) {  // HB = 3: all three B taps with the halo strip
+      with_bool(a.f16, [&](auto f16) {
+        with_bool(halo_hb(a, BN) == 3, [&](auto hb3) {
+          launch_fwd_kernel<BMT, BN, 1, F | kHalo | opt(f16.value, kF16), NT, hb3.value ? 3 : 1>(grid, s, a);
+        });
+      });
       return;
     }
   }
-  if constexpr (BMT == 128 && STAGES == 1 && LDSEPI && NT == conv::kThreads) {
+  if constexpr (kProd) {
     // (not with BNR2: that epilogue spills at the 128-VGPR bound of 4 waves per SIMD)
-    if constexpr (!BNR2) {
+    if constexpr (!has(F, kBnr2)) {
       if (g_conv_sk && !a.f16) {
         const int64_t tiles = (int64_t)a.m_tiles * a.n_tiles;
         const int G = conv_sk_blocks(tiles, (int)((int64_t)a.R * a.S * a.C / conv::BK), BN, g_conv_sk);
@@ -2398,37 +2499,17 @@ static void fwd_launch(dim3 grid, dim3 /*block*/, hipStream_t s, const ConvFwdAr
           a.sk.err = ws->flags + kSkMaxBlocks;
           a.sk.G = G;
           a.sk.part_bytes = (uint32_t)kSkPartBytes;
-          const dim3 sgrid((unsigned)(G + a.red.blocks));
-          hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, 1, true, BKN, STATS, BNB, BNR, REMAP, ZSIB, BNR2, false,
-                                              conv::kThreads, false, false, 1, true>),
-                             sgrid, block, 0, s, a);
+          launch_fwd_kernel<BMT, BN, 1, F | kSk>(dim3((unsigned)(G + a.red.blocks)), s, a);
           return;
         }
       }
     }
-    if (a.f16) {
-      hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, STAGES, LDSEPI, BKN, STATS, BNB, BNR, REMAP, ZSIB, BNR2, true>),
-                         grid, block, 0, s, a);
-      return;
-    }
+    with_bool(a.f16, [&](auto f16) { launch_fwd_kernel<BMT, BN, 1, F | opt(f16.value, kF16)>(grid, s, a); });
   } else {
     if (a.f16) throw std::runtime_error("conv: fp16 runs the default kernel variant only");
+    launch_fwd_kernel<BMT, BN, STAGES, F, NT>(grid, s, a);
   }
-  hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, STAGES, LDSEPI, BKN, STATS, BNB, BNR, REMAP, ZSIB, BNR2, false, NT>),
-                     grid, block, 0, s, a);
 }
-
-// ---- split-K for small grids ------------------------------------------------------------------
-// A conv whose 128 x BN tile grid is far below one block per CU (ResNet-18 on 32x32 images:
-// layer4 is 4 tiles at batch 128, each a 72-step K loop) is latency-bound on the K loop: split
-// the K-steps over blocks (fp32 partials, summed by conv_split_epilogue_kernel).  Target ~2
-// blocks per CU, at least 2 K-steps per split.  conv_set_splitk(0) disables it (A/B).
-// 0 = never split, 1 = auto (the policy below), 2 = the in-graph policy everywhere (tests that
-// compare eager with replayed steps); conv_set_splitk
-static int g_splitk = 1;
-static int splitk_mode() { return g_splitk; }
-void conv_set_splitk(int mode) { g_splitk = mode; }
-int conv_get_splitk() { return g_splitk; }
 
 int conv_fwd_splits(int64_t M, int Cout, int64_t K, int* kps_out, hipStream_t s) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -2437,24 +2518,12 @@ int conv_fwd_splits(int64_t M, int Cout, int64_t K, int* kps_out, hipStream_t s)
   return conv_fwd_splits_for(M, Cout, K, capturing, kps_out);
 }
 
-// Thresholds of the policy below: split grids of fewer than kSplitTiles tiles (eagerly: at most
-// kSplitEager tiles with >= 24 K-steps) to about kSplitTarget blocks (512 / 1024 targets
-// measured -1 % / -5 %, docs/DESIGN.md §7.2).
-static int kSplitTiles = 160, kSplitEager = 32, kSplitTarget = 512, kSplitEagerMinK = 24;
-// A/B knob (bench/ab_step.py): the thresholds above; a value <= 0 keeps the current one
-void conv_set_splitk_policy(int tiles, int eager_tiles, int eager_min_k, int target) {
-  if (tiles > 0) kSplitTiles = tiles;
-  if (eager_tiles > 0) kSplitEager = eager_tiles;
-  if (eager_min_k > 0) kSplitEagerMinK = eager_min_k;
-  if (target > 0) kSplitTarget = target;
-}
-
 int conv_fwd_splits_for(int64_t M, int Cout, int64_t K, bool graph, int* kps_out) {
   const int n_tiles = Cout % 128 == 0 ? Cout / 128 : Cout / 64;
   const int64_t tiles = (int64_t)conv_m_tiles(M) * n_tiles;
   const int nk = (int)(K / conv::BK);
   if (kps_out) *kps_out = nk;
-  const int mode = splitk_mode();
+  const int mode = g_splitk;
   if (mode == 0 || tiles >= kSplitTiles || nk < 4) return 1;
   // Eager launches are host-bound at these sizes: the extra epilogue launch only pays where the
   // single-block K loop is long (tens of microseconds); inside a hipGraph capture it always does.
@@ -2467,31 +2536,11 @@ int conv_fwd_splits_for(int64_t M, int Cout, int64_t K, bool graph, int* kps_out
   return splits;
 }
 
-template <int BN, bool STATS, bool BNB, bool BNR, bool BNR2, bool BKN = false, bool REMAP = false, bool ZSIB = false>
-static void split_launch(const ConvFwdArgs& a, hipStream_t s) {
-  ConvFwdArgs am = a;  // the main kernel takes an attached backward-weight reduce, the epilogue not
-  const dim3 grid((unsigned)(a.m_tiles * a.n_tiles * a.splits + take_attached_reduce(am))), block(conv::kThreads);
-  conv_check_offsets(a, BKN);
-  // the main loop's epilogue flags do not matter (SPLIT returns before it): one instantiation
-  if (a.f16)
-    hipLaunchKernelGGL((conv_fwd_kernel<128, BN, 1, true, BKN, false, false, false, false, false, false, true,
-                                        conv::kThreads, true>), grid, block, 0, s, am);
-  else
-    hipLaunchKernelGGL((conv_fwd_kernel<128, BN, 1, true, BKN, false, false, false, false, false, false, false,
-                                        conv::kThreads, true>), grid, block, 0, s, am);
-  const dim3 egrid((unsigned)((a.M + kSplitRows - 1) / kSplitRows), (unsigned)(a.Cout / 64));
-  if (a.f16)
-    hipLaunchKernelGGL((conv_split_epilogue_kernel<STATS, BNB, BNR, BNR2, REMAP, ZSIB, true>), egrid, dim3(256), 0, s,
-                       a);
-  else
-    hipLaunchKernelGGL((conv_split_epilogue_kernel<STATS, BNB, BNR, BNR2, REMAP, ZSIB, false>), egrid, dim3(256), 0, s,
-                       a);
-}
-
-// Launch the split-K path when the plan asks for it and a workspace was provided.  BNB
-// statistics go to columns [bp_off, bp_off + ceil(M/16)) of the [C][bp_ld] partial arrays.
-static bool maybe_split(ConvFwdArgs& a, float* ws, bool stats, bool bnb, bool bnr, bool bnr2, hipStream_t s,
-                        bool bkn = false, bool remap = false, bool zsib = false) {
+// Launch the split-K path (main kernel, then the epilogue kernel running epilogue F) when the
+// plan asks for it and a workspace was provided.  BNB statistics go to columns [bp_off, bp_off +
+// ceil(M/16)) of the [C][bp_ld] partial arrays.
+template <unsigned F>
+static bool maybe_split(ConvFwdArgs& a, float* ws, hipStream_t s) {
   if (ws == nullptr) return false;
   int kps = 0;
   const int splits = conv_fwd_splits(a.M, a.Cout, (int64_t)a.R * a.S * a.C, &kps, s);
@@ -2500,140 +2549,86 @@ static bool maybe_split(ConvFwdArgs& a, float* ws, bool stats, bool bnb, bool bn
   a.splits = splits;
   a.kps = kps;
   a.n_tiles = a.Cout % 128 == 0 ? a.Cout / 128 : a.Cout / 64;
-  const bool wide = a.Cout % 128 == 0;
-#define DPT_SPLIT(...)                                      \
-  do {                                                      \
-    if (wide) split_launch<128, __VA_ARGS__>(a, s);         \
-    else split_launch<64, __VA_ARGS__>(a, s);               \
-  } while (0)
-  if (remap) {
-    if (bnb) DPT_SPLIT(false, true, false, false, true, true, false);
-    else if (zsib) DPT_SPLIT(false, false, false, false, true, true, true);
-    else DPT_SPLIT(false, false, false, false, true, true, false);
-  } else if (stats) {
-    DPT_SPLIT(true, false, false, false);
-  } else if (bnb && bnr && bnr2) {
-    DPT_SPLIT(false, true, true, true);
-  } else if (bnb && bnr) {
-    DPT_SPLIT(false, true, true, false);
-  } else if (bnb) {
-    DPT_SPLIT(false, true, false, false);
-  } else {
-    DPT_SPLIT(false, false, false, false);
-  }
-#undef DPT_SPLIT
-  (void)bkn;
+  ConvFwdArgs am = a;  // the main kernel takes an attached backward-weight reduce, the epilogue not
+  const dim3 grid((unsigned)(a.m_tiles * a.n_tiles * a.splits + take_attached_reduce(am.red)));
+  const dim3 egrid((unsigned)((a.M + kSplitRows - 1) / kSplitRows), (unsigned)(a.Cout / 64));
+  conv_check_offsets(a, has(F, kBkn));
+  with_bool(a.f16, [&](auto f16) {
+    // the main loop's epilogue flags do not matter (SPLIT returns before it): one instantiation
+    constexpr unsigned kMain = kLdsEpi | kSplit | (F & kBkn) | opt(f16.value, kF16);
+    with_bool(a.Cout % 128 == 0,
+              [&](auto wide) { launch_fwd_kernel<128, wide.value ? 128 : 64, 1, kMain>(grid, s, am); });
+    launch_split_epilogue_kernel<F | opt(f16.value, kF16)>(egrid, s, a);
+  });
   return true;
 }
 
 template <int BMW, int BNW, int STAGES>
-static void wgrad_launch(dim3 grid, dim3 block, hipStream_t s, const ConvWgradArgs& a) {
+static void wgrad_launch(dim3 grid, hipStream_t s, const ConvWgradArgs& a) {
   if constexpr (STAGES == 1) {
-    if (a.direct && !a.f16) {
-      hipLaunchKernelGGL((conv_wgrad_kernel<BMW, BNW, STAGES, false, conv::kThreads, true>), grid, block, 0, s, a);
-      return;
-    }
-    if (a.f16) {
-      hipLaunchKernelGGL((conv_wgrad_kernel<BMW, BNW, STAGES, true>), grid, block, 0, s, a);
-      return;
-    }
+    if (a.direct && !a.f16) return launch_wgrad_kernel<BMW, BNW, STAGES, kDir>(grid, s, a);
+    if (a.f16) return launch_wgrad_kernel<BMW, BNW, STAGES, kF16>(grid, s, a);
   } else {
     if (a.f16) throw std::runtime_error("conv_wgrad: fp16 runs the default kernel variant only");
   }
-  hipLaunchKernelGGL((conv_wgrad_kernel<BMW, BNW, STAGES, false>), grid, block, 0, s, a);
+  launch_wgrad_kernel<BMW, BNW, STAGES, 0u>(grid, s, a);
 }
 
-template <int BN>
+// The 4-wave tiles of conv_set_variant (E: kStats or nothing, by a.psum - only the production tile
+// is compiled without the statistics epilogue; the others test psum at run time).
+template <int BN, unsigned E>
 static void conv_fwd_dispatch(int variant, bool bkn, ConvFwdArgs a, hipStream_t s) {
   if (a.f16) variant = 4;
   if (variant == 0) variant = 4;  // measured best at every ResNet-50 shape but two (profiles/conv_*.md)
-  const dim3 block(conv::kThreads);
-  const int mt128 = a.m_tiles;
   if (variant >= 5 && !bkn) {  // 256-row blocks (4 row tiles per wave)
-    a.mt256 = (mt128 + 1) / 2;  // m_tiles stays the 128-row count: the BN-partials layout
+    a.mt256 = (a.m_tiles + 1) / 2;  // m_tiles stays the 128-row count: the BN-partials layout
     const dim3 grid((unsigned)(a.mt256 * a.n_tiles));
-    if (variant == 5) fwd_launch<256, BN, 1, false, false>(grid, block, s, a);
-    else fwd_launch<256, BN, 1, true, false>(grid, block, s, a);
+    if (variant == 5) fwd_launch<256, BN, 1, kStats>(grid, s, a);
+    else fwd_launch<256, BN, 1, kLdsEpi | kStats>(grid, s, a);
     return;
   }
   const dim3 grid((unsigned)(a.m_tiles * a.n_tiles));
-  const int nk32 = a.R * a.S * (a.C / 32);
+  // (not reached: the 256-row test above takes these codes; the pipelined kernels stay compiled)
   if (!bkn && (variant == 7 || variant == 8 || variant == 14)) {
-    const bool st = a.psum != nullptr;
-    if (variant == 14) {  // 2-stage BK = 32 ring: the same 32 KiB of operand LDS as the 1-stage tile
-      if (st) hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN, 2, true>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN, 2, false>), grid, block, 0, s, a);
-    } else if (variant == 7) {
-      if (st) hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN, 3, true>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN, 3, false>), grid, block, 0, s, a);
-    } else {
-      if (st) hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN, 4, true>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN, 4, false>), grid, block, 0, s, a);
-    }
+    const dim3 block(conv::kThreads);
+    // 14: 2-stage BK = 32 ring: the same 32 KiB of operand LDS as the 1-stage tile
+    if (variant == 14) hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN, 2, has(E, kStats)>), grid, block, 0, s, a);
+    else if (variant == 7) hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN, 3, has(E, kStats)>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((conv_fwd_pipe_kernel<BN, 4, has(E, kStats)>), grid, block, 0, s, a);
     return;
   }
-  (void)nk32;
   if (bkn) {
-    fwd_launch<128, BN, 1, true, true>(grid, block, s, a);
+    fwd_launch<128, BN, 1, kLdsEpi | kBkn | kStats>(grid, s, a);
     return;
   }
   switch (variant) {
-    case 2: fwd_launch<128, BN, 2, false, false>(grid, block, s, a); break;
-    case 3: fwd_launch<128, BN, 1, false, false>(grid, block, s, a); break;
-    case 4:
-      if (a.psum) fwd_launch<128, BN, 1, true, false, true>(grid, block, s, a);
-      else fwd_launch<128, BN, 1, true, false, false>(grid, block, s, a);
-      break;
-    default: fwd_launch<128, BN, 2, true, false>(grid, block, s, a); break;
+    case 2: fwd_launch<128, BN, 2, kStats>(grid, s, a); break;
+    case 3: fwd_launch<128, BN, 1, kStats>(grid, s, a); break;
+    case 4: fwd_launch<128, BN, 1, kLdsEpi | E>(grid, s, a); break;
+    default: fwd_launch<128, BN, 2, kLdsEpi | kStats>(grid, s, a); break;
   }
 }
 
-// 8-wave (512-thread) variants: 9 = 256x256 tile, 10 = 256x128, 11 = 128x256 (2 stages);
-// 12 = 256x128, 13 = 128x256 with the 3-stage pipelined K loop (two K-tiles in flight across
-// one raw barrier per step).  Returns false when the shape does not fit the variant's N tile.
-static int big_bn(int v) { return (v == 10 || v == 12) ? 128 : 256; }
-static int big_bm(int v) { return (v == 11 || v == 13) ? 128 : 256; }
+// 8-wave (512-thread) variants with epilogue E: 9 = 256x256 tile, 10 = 256x128, 11 = 128x256 (2
+// stages); 12 = 256x128, 13 = 128x256 with the 3-stage pipelined K loop (two K-tiles in flight
+// across one raw barrier per step).  Returns false when the shape does not fit the variant's N
+// tile, or for variant 11 with a BNB epilogue (compiled for the forward epilogues only).
+template <unsigned E>
 static bool conv_fwd_big(int v, ConvFwdArgs& a, hipStream_t s) {
-  const int bn = big_bn(v), bm = big_bm(v);
-  if (a.Cout % bn) return false;
+  const int bn = (v == 10 || v == 12) ? 128 : 256, bm = (v == 11 || v == 13) ? 128 : 256;
+  if (a.Cout % bn || (v == 11 && has(E, kBnb))) return false;
   a.n_tiles = a.Cout / bn;
   a.mt256 = (int)((a.M + 255) / 256);
-  const int mt = bm == 256 ? a.mt256 : a.m_tiles;
-  const dim3 grid((unsigned)(mt * a.n_tiles)), block(512);
-  const bool st = a.psum != nullptr;
-  if (v == 12) {
-    if (st) fwd_launch<256, 128, 3, true, false, true, false, false, false, false, false, 512>(grid, block, s, a);
-    else fwd_launch<256, 128, 3, true, false, false, false, false, false, false, false, 512>(grid, block, s, a);
-  } else if (v == 13) {
-    if (st) fwd_launch<128, 256, 3, true, false, true, false, false, false, false, false, 512>(grid, block, s, a);
-    else fwd_launch<128, 256, 3, true, false, false, false, false, false, false, false, 512>(grid, block, s, a);
-  } else if (v == 9) {
-    if (st) fwd_launch<256, 256, 2, true, false, true, false, false, false, false, false, 512>(grid, block, s, a);
-    else fwd_launch<256, 256, 2, true, false, false, false, false, false, false, false, 512>(grid, block, s, a);
-  } else if (v == 10) {
-    if (st) fwd_launch<256, 128, 2, true, false, true, false, false, false, false, false, 512>(grid, block, s, a);
-    else fwd_launch<256, 128, 2, true, false, false, false, false, false, false, false, 512>(grid, block, s, a);
-  } else {
-    if (st) fwd_launch<128, 256, 2, true, false, true, false, false, false, false, false, 512>(grid, block, s, a);
-    else fwd_launch<128, 256, 2, true, false, false, false, false, false, false, false, 512>(grid, block, s, a);
-  }
+  const dim3 grid((unsigned)((bm == 256 ? a.mt256 : a.m_tiles) * a.n_tiles));
+  constexpr unsigned F = kLdsEpi | E;
+  if (v == 12) fwd_launch<256, 128, 3, F, 512>(grid, s, a);
+  else if (v == 13) fwd_launch<128, 256, 3, F, 512>(grid, s, a);
+  else if (v == 9) fwd_launch<256, 256, 2, F, 512>(grid, s, a);
+  else if (v == 10) fwd_launch<256, 128, 2, F, 512>(grid, s, a);
+  else if constexpr (!has(E, kBnb)) fwd_launch<128, 256, 2, F, 512>(grid, s, a);
   return true;
 }
 
-// Per-shape forward tile policy (variant 0 only; bits, conv_set_fwd_shape_policy):
-//   1: expanding 1x1 convs with the BN-statistics epilogue (C <= 128, Cout >= 2C) -> 256-row
-//      blocks with the LDS epilogue (variant 6): the statistics partials are summed over 256
-//      rows per block instead of 128 (64->256 @56: 0.155 -> 0.130 ms with statistics, MIOpen
-//      0.106 without; bench/conv_variant_sweep.py, profiles/conv_variant_sweep_r4.md);
-//   2: the 3x3 stride-2 256->256 conv (K = 2304, M >= 32768) -> the 8-wave 256x256 tile (variant
-//      9): 0.081 -> 0.069 ms, 1.05-1.08x MIOpen.
-//   16: the s2d stem's 4x4 conv (C = 16) on the 2-stage K loop (variant 1).
-//   4 / 8: 1x1 stride-1 convs with the statistics epilogue on grids under 1,024 tiles (the deep
-//      reducing convs at 14x14 / 7x7, latency-bound with ~3 resident blocks per CU:
-//      profiles/step_pmc_r5.md) -> the BK = 32 pipelined K loop, 2 stages (variant 14, 4 blocks
-//      per CU) / 3 stages (variant 7).
-static int g_fwd_shape_policy = 0;
-void conv_set_fwd_shape_policy(int bits) { g_fwd_shape_policy = bits; }
 static int fwd_shape_variant(const ConvFwdArgs& a, bool stats) {
   if (a.f16) return 0;
   if ((g_fwd_shape_policy & 1) && stats && a.R == 1 && a.S == 1 && a.stride == 1 && a.C <= 128 &&
@@ -2650,32 +2645,49 @@ static int fwd_shape_variant(const ConvFwdArgs& a, bool stats) {
   return 0;
 }
 
+// The fields every launcher fills the same way: the conv of x [N, H, W, C] with an R x S weight
+// to y [N, Ho, Wo, Cout], and the BKN tap map of a stride-1 backward-data (all taps, flipped).
+static ConvFwdArgs conv_args(const uint16_t* x, const uint16_t* w, uint16_t* y, bool f16, int N, int H, int W, int C,
+                             int Cout, int R, int S, int stride, int pad, int Ho, int Wo) {
+  ConvFwdArgs a;
+  a.f16 = f16 ? 1 : 0;
+  a.x = x; a.w = w; a.y = y;
+  a.N = N; a.H = H; a.W = W; a.C = C; a.Cout = Cout; a.R = R; a.S = S; a.stride = stride; a.pad = pad;
+  a.Ho = Ho; a.Wo = Wo;
+  a.M = (int64_t)N * Ho * Wo;
+  a.m_tiles = conv_m_tiles(a.M);
+  a.Rw = R; a.Sw = S; a.tr0 = R - 1; a.trs = -1; a.ts0 = S - 1; a.tss = -1;
+  return a;
+}
+
+// The default 128 x (128 | 64) tile with epilogue F (1 stage, LDS epilogue), by the width of Cout.
+template <unsigned F>
+static void fwd_launch_default(ConvFwdArgs& a, hipStream_t s) {
+  a.n_tiles = a.Cout % 128 == 0 ? a.Cout / 128 : a.Cout / 64;
+  const dim3 grid((unsigned)(a.m_tiles * a.n_tiles));
+  with_bool(a.Cout % 128 == 0, [&](auto wide) { fwd_launch<128, wide.value ? 128 : 64, 1, kLdsEpi | F>(grid, s, a); });
+}
+
 static void conv_fwd_impl(const uint16_t* x, const uint16_t* w, uint16_t* y, int N, int H, int W, int C, int Cout,
                           int R, int S, int stride, int pad, float* psum, float* psq, bool bkn, hipStream_t s,
                           int Ho = 0, int Wo = 0, bool f16 = false, float* ws = nullptr) {
-  ConvFwdArgs a;
-  a.part = nullptr; a.splits = 1; a.kps = 0;
-  a.f16 = f16 ? 1 : 0;
-  a.x = x; a.w = w; a.y = y; a.psum = psum; a.psq = psq;
-  a.N = N; a.H = H; a.W = W; a.C = C; a.Cout = Cout; a.R = R; a.S = S; a.stride = stride; a.pad = pad;
   // explicit output size: asymmetric padding (pad on top/left only, e.g. the space-to-depth stem)
-  a.Ho = Ho > 0 ? Ho : (H + 2 * pad - R) / stride + 1;
-  a.Wo = Wo > 0 ? Wo : (W + 2 * pad - S) / stride + 1;
-  a.M = (int64_t)N * a.Ho * a.Wo;
-  a.m_tiles = conv_m_tiles(a.M);
-  a.Rw = R; a.Sw = S; a.tr0 = R - 1; a.trs = -1; a.ts0 = S - 1; a.tss = -1;  // BKN: flipped taps
+  ConvFwdArgs a = conv_args(x, w, y, f16, N, H, W, C, Cout, R, S, stride, pad,
+                            Ho > 0 ? Ho : (H + 2 * pad - R) / stride + 1, Wo > 0 ? Wo : (W + 2 * pad - S) / stride + 1);
+  a.psum = psum; a.psq = psq;
   const bool wide = Cout % 128 == 0;
   a.n_tiles = Cout / (wide ? 128 : 64);
-  a.mt256 = 0;
-  int v = fwd_variant();
-  if (!bkn && maybe_split(a, ws, psum != nullptr, false, false, false, s)) return;
-  if (!bkn && v == 0) v = fwd_shape_variant(a, psum != nullptr);
-  if (!bkn && !a.f16) {
-    const int vb = (v >= 9 && v <= 13) ? v : v == 0 ? conv_big_auto(a.M, Cout, (int64_t)R * S * C, R * S) : 0;
-    if (vb && conv_fwd_big(vb, a, s)) return;
-  }
-  if (wide) conv_fwd_dispatch<128>(v, bkn, a, s);
-  else conv_fwd_dispatch<64>(v, bkn, a, s);
+  with_bool(psum != nullptr, [&](auto stats) {
+    constexpr unsigned E = opt(stats.value, kStats);
+    int v = fwd_variant();
+    if (!bkn && maybe_split<E>(a, ws, s)) return;
+    if (!bkn && v == 0) v = fwd_shape_variant(a, stats.value);
+    if (!bkn && !a.f16) {
+      const int vb = (v >= 9 && v <= 13) ? v : v == 0 ? conv_big_auto(a.M, Cout, (int64_t)R * S * C, R * S) : 0;
+      if (vb && conv_fwd_big<E>(vb, a, s)) return;
+    }
+    with_bool(wide, [&](auto w128) { conv_fwd_dispatch<w128.value ? 128 : 64, E>(v, bkn, a, s); });
+  });
 }
 
 // Stride-1 backward-data through a flipped/transposed weight wt [C][R][S][Cout] (the forward
@@ -2686,71 +2698,29 @@ void launch_conv_dgrad_bnstats(const uint16_t* dy, const uint16_t* wt, uint16_t*
                                const float* bn_coef, float* bp1, float* bp2, hipStream_t s,
                                const uint16_t* bny, const uint16_t* bnres, const uint16_t* bnx2,
                                const float* bn_mean2, float* bp3, bool f16, float* ws, const uint8_t* bnmask) {
-  ConvFwdArgs a;
-  a.part = nullptr; a.splits = 1; a.kps = 0;
-  a.f16 = f16 ? 1 : 0;
-  a.x = dy; a.w = wt; a.y = dx; a.psum = nullptr; a.psq = nullptr;
-  a.N = N; a.H = Ho; a.W = Wo; a.C = Cout; a.Cout = C; a.R = R; a.S = S; a.stride = 1; a.pad = R - 1 - pad;
-  a.Ho = Ho + 2 * a.pad - R + 1;
-  a.Wo = Wo + 2 * a.pad - S + 1;
-  a.M = (int64_t)N * a.Ho * a.Wo;
-  a.m_tiles = conv_m_tiles(a.M);
-  a.mt256 = 0;
+  const int padb = R - 1 - pad;
+  ConvFwdArgs a = conv_args(dy, wt, dx, f16, N, Ho, Wo, Cout, C, R, S, 1, padb, Ho + 2 * padb - R + 1,
+                            Wo + 2 * padb - S + 1);
   a.bnx = bnx; a.bn_mean = bn_mean; a.bn_coef = bn_coef; a.bp1 = bp1; a.bp2 = bp2;
   a.bny = bny; a.bnres = bnres; a.bnmask = bnmask;
   a.bnx2 = bnx2; a.bn_mean2 = bn_mean2; a.bp3 = bp3;
-  a.bp_ld = a.m_tiles; a.bp_off = 0;
-  const bool res = bny != nullptr;
-  const dim3 block(conv::kThreads);
-  {
-    const int64_t keep_ld = a.bp_ld;
+  const auto run = [&](auto epi) {
+    constexpr unsigned E = decltype(epi)::value;
     a.bp_ld = conv_split_cols(a.M);  // split: one partial column per 16-row slab
-    if (maybe_split(a, ws, false, true, res, res && bnx2 != nullptr, s)) return;
-    a.bp_ld = keep_ld;
-  }
-  const bool two = res && bnx2 != nullptr;
-  const int cv = fwd_variant();
-  if (!f16 && (cv == 0 || (cv >= 9 && cv <= 13))) {
-    // 8-wave tiles (conv_big_auto, or a forced variant): N = C, K = Cout*R*S
-    const int vb = cv ? cv : conv_big_auto(a.M, C, (int64_t)Cout * R * S, R * S);
-    if (vb && C % big_bn(vb) == 0) {
-      const int bn = big_bn(vb), bm = big_bm(vb);
-      a.n_tiles = C / bn;
-      a.mt256 = (int)((a.M + 255) / 256);
-      const dim3 g((unsigned)((bm == 256 ? a.mt256 : a.m_tiles) * a.n_tiles));
-      if (vb == 12) {
-        if (two) fwd_launch<256, 128, 3, true, false, false, true, true, false, false, true, 512>(g, block, s, a);
-        else if (res) fwd_launch<256, 128, 3, true, false, false, true, true, false, false, false, 512>(g, block, s, a);
-        else fwd_launch<256, 128, 3, true, false, false, true, false, false, false, false, 512>(g, block, s, a);
-      } else if (vb == 13) {
-        if (two) fwd_launch<128, 256, 3, true, false, false, true, true, false, false, true, 512>(g, block, s, a);
-        else if (res) fwd_launch<128, 256, 3, true, false, false, true, true, false, false, false, 512>(g, block, s, a);
-        else fwd_launch<128, 256, 3, true, false, false, true, false, false, false, false, 512>(g, block, s, a);
-      } else if (vb == 9) {
-        if (two) fwd_launch<256, 256, 2, true, false, false, true, true, false, false, true, 512>(g, block, s, a);
-        else if (res) fwd_launch<256, 256, 2, true, false, false, true, true, false, false, false, 512>(g, block, s, a);
-        else fwd_launch<256, 256, 2, true, false, false, true, false, false, false, false, 512>(g, block, s, a);
-      } else if (vb == 10) {
-        if (two) fwd_launch<256, 128, 2, true, false, false, true, true, false, false, true, 512>(g, block, s, a);
-        else if (res) fwd_launch<256, 128, 2, true, false, false, true, true, false, false, false, 512>(g, block, s, a);
-        else fwd_launch<256, 128, 2, true, false, false, true, false, false, false, false, 512>(g, block, s, a);
-      } else {
-        a.n_tiles = 0;  // unsupported forced variant for this pass: fall through to the default
-      }
-      if (a.n_tiles) return;
+    if (maybe_split<E>(a, ws, s)) return;
+    a.bp_ld = a.m_tiles;
+    const int cv = fwd_variant();
+    if (!f16 && (cv == 0 || (cv >= 9 && cv <= 13))) {
+      // 8-wave tiles (conv_big_auto, or a forced variant): N = C, K = Cout*R*S
+      const int vb = cv ? cv : conv_big_auto(a.M, C, (int64_t)Cout * R * S, R * S);
+      if (vb && conv_fwd_big<E>(vb, a, s)) return;
     }
-  }
-  a.n_tiles = C % 128 == 0 ? C / 128 : C / 64;
-  const dim3 grid((unsigned)(a.m_tiles * a.n_tiles));
-  if (C % 128 == 0) {
-    if (two) fwd_launch<128, 128, 1, true, false, false, true, true, false, false, true>(grid, block, s, a);
-    else if (res) fwd_launch<128, 128, 1, true, false, false, true, true>(grid, block, s, a);
-    else fwd_launch<128, 128, 1, true, false, false, true>(grid, block, s, a);
-  } else {
-    if (two) fwd_launch<128, 64, 1, true, false, false, true, true, false, false, true>(grid, block, s, a);
-    else if (res) fwd_launch<128, 64, 1, true, false, false, true, true>(grid, block, s, a);
-    else fwd_launch<128, 64, 1, true, false, false, true>(grid, block, s, a);
-  }
+    fwd_launch_default<E>(a, s);
+  };
+  const bool res = bny != nullptr;
+  if (res && bnx2 != nullptr) run(Opts<kBnb | kBnr | kBnr2>{});
+  else if (res) run(Opts<kBnb | kBnr>{});
+  else run(Opts<kBnb>{});
 }
 
 // A Linear's backward-data with the exact-GELU backward of its input fused into the epilogue
@@ -2761,27 +2731,15 @@ void launch_linear_dgrad_dgelu(const uint16_t* dy, const uint16_t* wt, const uin
                                const uint16_t* bias16, uint16_t* gu, float* bp1, int64_t T, int n_out, int n_in,
                                bool f16, hipStream_t s) {
   if (n_in % 128 != 0 || n_out % 64 != 0) throw std::runtime_error("linear_dgrad_dgelu: n_in % 128, n_out % 64");
-  ConvFwdArgs a;
-  a.part = nullptr; a.splits = 1; a.kps = 0;
-  a.f16 = f16 ? 1 : 0;
-  a.x = dy; a.w = wt; a.y = gu; a.psum = nullptr; a.psq = nullptr;
-  a.N = 1; a.H = 1; a.W = (int)T; a.C = n_out; a.Cout = n_in; a.R = 1; a.S = 1; a.stride = 1; a.pad = 0;
-  a.Ho = 1; a.Wo = (int)T;
-  a.M = T;
-  a.m_tiles = conv_m_tiles(a.M);
-  a.mt256 = 0;
+  ConvFwdArgs a = conv_args(dy, wt, gu, f16, 1, 1, (int)T, n_out, n_in, 1, 1, 1, 0, 1, (int)T);
   a.n_tiles = n_in / 128;
-  a.bnx = u; a.bn_mean = bias; a.bias16 = bias16; a.bn_coef = nullptr; a.bp1 = bp1; a.bp2 = nullptr;
-  a.bny = nullptr; a.bnres = nullptr; a.bnmask = nullptr; a.bnx2 = nullptr; a.bn_mean2 = nullptr; a.bp3 = nullptr;
-  a.bp_ld = a.m_tiles; a.bp_off = 0;
+  a.bnx = u; a.bn_mean = bias; a.bias16 = bias16; a.bp1 = bp1;
+  a.bp_ld = a.m_tiles;
   conv_check_offsets(a, false);
-  const dim3 grid((unsigned)(a.m_tiles * a.n_tiles)), block(conv::kThreads);
-  if (f16)
-    hipLaunchKernelGGL((conv_fwd_kernel<128, 128, 1, true, false, false, true, false, false, false, false, true,
-                                        conv::kThreads, false, false, 1, false, true>), grid, block, 0, s, a);
-  else
-    hipLaunchKernelGGL((conv_fwd_kernel<128, 128, 1, true, false, false, true, false, false, false, false, false,
-                                        conv::kThreads, false, false, 1, false, true>), grid, block, 0, s, a);
+  const dim3 grid((unsigned)(a.m_tiles * a.n_tiles));
+  with_bool(f16, [&](auto h) {
+    launch_fwd_kernel<128, 128, 1, kLdsEpi | kBnb | kDgelu | opt(h.value, kF16)>(grid, s, a);
+  });
 }
 
 int linear_dgrad_dgelu_tiles(int64_t T) { return conv_m_tiles(T); }
@@ -2869,63 +2827,36 @@ void launch_conv_dgrad_s2(const uint16_t* dy, const uint16_t* w, uint16_t* dx, i
   const int ncl = s2_classes(H, W, R, S, pad, cl);
   for (int ci = 0; ci < ncl; ++ci) {
     const S2Class& k = cl[ci];
-    ConvFwdArgs a;
-    a.part = nullptr; a.splits = 1; a.kps = 0;
-    a.f16 = f16 ? 1 : 0;
-    a.x = dy; a.w = w; a.y = dx; a.psum = nullptr; a.psq = nullptr;
-    a.N = N; a.H = Ho; a.W = Wo; a.C = Cout; a.Cout = C; a.R = k.Rc; a.S = k.Sc; a.stride = 1;
-    a.pad = k.pad;
-    a.Ho = k.Ha; a.Wo = k.Wa;
-    a.M = (int64_t)N * k.Ha * k.Wa;
-    a.m_tiles = conv_m_tiles(a.M);
-    a.mt256 = 0;
+    ConvFwdArgs a = conv_args(dy, w, dx, f16, N, Ho, Wo, Cout, C, k.Rc, k.Sc, 1, k.pad, k.Ha, k.Wa);
     a.Rw = R; a.Sw = S;
     a.tr0 = k.tr0; a.trs = -2;
     a.ts0 = k.ts0; a.tss = -2;
     a.oH = H; a.oW = W; a.oph = k.ph; a.opw = k.pw;
-    a.bnx = bnx; a.bny = nullptr; a.bnres = nullptr; a.bn_mean = bn_mean; a.bn_coef = bn_coef;
-    a.bnx2 = nullptr; a.bn_mean2 = nullptr; a.bp3 = nullptr;
+    a.bnx = bnx; a.bn_mean = bn_mean; a.bn_coef = bn_coef;
     a.bp1 = bp1; a.bp2 = bp2; a.bp_ld = bp_ld; a.bp_off = bp_off;
-    const bool z = k.zsib;
     // zero classes (ZSIB) only arise for 1x1 kernels, whose input is never a fused BN+ReLU output
     // in the models here: BNB and ZSIB are not combined
-    if (bnb && z) throw std::runtime_error("conv_dgrad_s2: BN statistics with zero-filled classes unsupported");
-    if (maybe_split(a, ws, false, bnb, false, false, s, true, true, z)) {
-      bp_off += conv_split_cols(a.M);
-      continue;
-    }
-    bp_off += a.m_tiles;
-    const dim3 block(conv::kThreads);
-    a.n_tiles = C % 128 == 0 ? C / 128 : C / 64;
-    const dim3 grid((unsigned)(a.m_tiles * a.n_tiles));
-    if (bnb) {
-      if (C % 128 == 0) fwd_launch<128, 128, 1, true, true, false, true, false, true, false>(grid, block, s, a);
-      else fwd_launch<128, 64, 1, true, true, false, true, false, true, false>(grid, block, s, a);
-      continue;
-    }
-    if (C % 128 == 0) {
-      if (z) fwd_launch<128, 128, 1, true, true, false, false, false, true, true>(grid, block, s, a);
-      else fwd_launch<128, 128, 1, true, true, false, false, false, true, false>(grid, block, s, a);
-    } else {
-      if (z) fwd_launch<128, 64, 1, true, true, false, false, false, true, true>(grid, block, s, a);
-      else fwd_launch<128, 64, 1, true, true, false, false, false, true, false>(grid, block, s, a);
-    }
+    if (bnb && k.zsib) throw std::runtime_error("conv_dgrad_s2: BN statistics with zero-filled classes unsupported");
+    const auto run = [&](auto epi) {
+      constexpr unsigned F = kBkn | kRemap | decltype(epi)::value;
+      if (maybe_split<F>(a, ws, s)) {
+        bp_off += conv_split_cols(a.M);
+        return;
+      }
+      bp_off += a.m_tiles;
+      fwd_launch_default<F>(a, s);
+    };
+    if (bnb) run(Opts<kBnb>{});
+    else if (k.zsib) run(Opts<kZsib>{});
+    else run(Opts<0u>{});
   }
 }
 
-// conv_wgrad_halo_kernel modes: 0 off, 1 / 2: 128-channel strips, 3 / 4: 64-channel strips
-// (even: double-buffered), 5 auto (default; conv_set_wgrad_halo for A/B): mode 3 for 64-channel inputs,
-// where the per-tap kernel's two-tap tiles waste 1/9 of their MFMA work on a ragged last tile
-// (64x56x56 -> 64: 0.118 -> 0.085-0.095 ms); the per-tap kernel elsewhere (the halo's W+2
-// padding costs 7-29 % more MFMA work and measured level or slower at 128-512 channels,
-// profiles/wgrad_halo_r2.md)
-static int g_wgrad_halo = 5;
-static int wgrad_halo_mode(int C = 0) {
+static int wgrad_halo_mode(int C) {
   if (g_wgrad_halo == 5) return C == 64 ? 3 : 0;
   if (g_wgrad_halo == 6) return C == 64 ? 4 : 0;  // A/B: the double-buffered strip on the same convs
   return g_wgrad_halo;
 }
-void conv_set_wgrad_halo(int on) { g_wgrad_halo = on; }
 
 static FastDiv make_fastdiv(uint32_t d) {
   FastDiv f;
@@ -2940,20 +2871,6 @@ static FastDiv make_fastdiv(uint32_t d) {
   return f;
 }
 
-// Block target of the split-K backward-weight plan.  Measured per ResNet-50 shape at batch 256
-// (bench/wgrad_target_sweep.py, profiles/wgrad_target_sweep_r3.md): 1x1 / stride-1 convs (one
-// tap, streaming both operands once) want ~512 blocks - fewer fp32 partial tiles to write and
-// reduce; convs with taps or a stride want more blocks to hide their K loop, 768 on the long
-// (>= 3136 K-step) reductions and 640 on the shorter ones.  Step total 3.65 -> 3.49 ms.
-// conv_set_wgrad_target(n > 0): n blocks for every shape (the sweep); 0: this policy.
-static int g_wgrad_target = 0;
-void conv_set_wgrad_target(int blocks) { g_wgrad_target = blocks; }
-// backward-weight K loop depth (A/B, conv_set_wgrad_stages): 0 = the single-stage tile (4 blocks
-// per CU); 1 = the double-buffered tile (2 blocks per CU) for grids of at most one wave at 2
-// blocks per CU - there residency is set by the grid, not by LDS, so the deeper pipeline costs
-// no resident block; 2 = double-buffered everywhere
-static int g_wgrad_stages = 0;
-void conv_set_wgrad_stages(int mode) { g_wgrad_stages = mode; }
 static int wgrad_target(int R, int S, int stride, int steps) {
   if (g_wgrad_target > 0) return g_wgrad_target;
   if (R * S == 1 && stride == 1) return 512;
@@ -2993,7 +2910,7 @@ ConvWgradPlan conv_wgrad_plan(int N, int H, int W, int C, int Cout, int R, int S
   pl.bnw = C % 128 == 0 ? 128 : (C == 64 && R * S > 1) ? 128 : (C == 16 && R * S * C >= 256 && pl.bmw == 64) ? 256 : 64;
   // variant 20 (A/B, bench/wgrad_variants.py): 8-wave 256 x 256 tiles where both channel counts
   // allow them.  Its own code: 10-13 select forward/dgrad tile variants (conv_fwd_big).
-  if (conv_variant() == 20 && Cout % 256 == 0 && C % 256 == 0) pl.bmw = pl.bnw = 256;
+  if (g_conv_variant == 20 && Cout % 256 == 0 && C % 256 == 0) pl.bmw = pl.bnw = 256;
   const int tiles = (Cout / pl.bmw) * ((R * S * C + pl.bnw - 1) / pl.bnw);
   const int steps = (int)((M + 63) / 64);
   // ~768 blocks (3 per CU) and at least 32 K-steps per split: a split's fp32 partial tile
@@ -3051,38 +2968,35 @@ void launch_conv_wgrad(const uint16_t* dy, const uint16_t* x, float* part, void*
     a.div_wp = make_fastdiv((uint32_t)(W + 2));
     a.div_h = make_fastdiv((uint32_t)H);
   }
-  dim3 grid((unsigned)(a.co_tiles * a.n_tiles * a.splits)), block(conv::kThreads);
+  const dim3 grid((unsigned)(a.co_tiles * a.n_tiles * a.splits));
   const int v = a.f16 ? 0 : fwd_variant();
-  if (pl.halo) {
-#define DPT_WH(BNW, ST)                                                                      \
-  do {                                                                                       \
-    if (a.f16) hipLaunchKernelGGL((conv_wgrad_halo_kernel<BNW, ST, true>), grid, block, 0, st, a);  \
-    else hipLaunchKernelGGL((conv_wgrad_halo_kernel<BNW, ST, false>), grid, block, 0, st, a);       \
-  } while (0)
-    switch (pl.halo) {
-      case 2: DPT_WH(128, 2); break;
-      case 3: DPT_WH(64, 1); break;
-      case 4: DPT_WH(64, 2); break;
-      default: DPT_WH(128, 1); break;
-    }
-#undef DPT_WH
+  // 2-stage K loop: variants 1 / 2, or conv_set_wgrad_stages (bf16, tiles up to 128 columns)
+  const bool two_stage =
+      (v == 1 || v == 2 || (!a.f16 && (g_wgrad_stages == 2 || (g_wgrad_stages == 1 && grid.x <= 2u * 256u)))) &&
+      pl.bnw <= 128;
+  if (pl.halo) {  // modes 3 / 4: 64-channel strips, 2 / 4: double-buffered
+    with_bool(pl.halo == 3 || pl.halo == 4, [&](auto narrow) {
+      with_bool(pl.halo == 2 || pl.halo == 4, [&](auto dbuf) {
+        with_bool(a.f16, [&](auto h) {
+          launch_wgrad_halo_kernel<narrow.value ? 64 : 128, dbuf.value ? 2 : 1, opt(h.value, kF16)>(grid, st, a);
+        });
+      });
+    });
   } else if (pl.bmw == 256 && pl.bnw == 64) {
-    wgrad_launch<256, 64, 1>(grid, block, st, a);
+    wgrad_launch<256, 64, 1>(grid, st, a);
   } else if (pl.bmw == 256) {  // conv_wgrad_plan chose the 8-wave 256 x 256 tile
     if (a.f16) throw std::runtime_error("conv_wgrad: the 256 x 256 variant is bf16 only");
-    hipLaunchKernelGGL((conv_wgrad_kernel<256, 256, 2, false, 512>), grid, dim3(512), 0, st, a);
-  } else if ((v == 1 || v == 2 || (!a.f16 && (g_wgrad_stages == 2 ||
-                                             (g_wgrad_stages == 1 && grid.x <= 2u * 256u)))) && pl.bnw <= 128) {
-    if (pl.bmw == 128 && pl.bnw == 128) wgrad_launch<128, 128, 2>(grid, block, st, a);
-    else if (pl.bmw == 128) wgrad_launch<128, 64, 2>(grid, block, st, a);
-    else if (pl.bnw == 128) wgrad_launch<64, 128, 2>(grid, block, st, a);
-    else wgrad_launch<64, 64, 2>(grid, block, st, a);
+    launch_wgrad_kernel<256, 256, 2, 0u, 512>(grid, st, a);
+  } else if (!two_stage && pl.bmw != 128 && pl.bnw == 256) {
+    wgrad_launch<64, 256, 1>(grid, st, a);
   } else {
-    if (pl.bmw == 128 && pl.bnw == 128) wgrad_launch<128, 128, 1>(grid, block, st, a);
-    else if (pl.bmw == 128) wgrad_launch<128, 64, 1>(grid, block, st, a);
-    else if (pl.bnw == 256) wgrad_launch<64, 256, 1>(grid, block, st, a);
-    else if (pl.bnw == 128) wgrad_launch<64, 128, 1>(grid, block, st, a);
-    else wgrad_launch<64, 64, 1>(grid, block, st, a);
+    with_bool(two_stage, [&](auto two) {
+      with_bool(pl.bmw == 128, [&](auto m128) {
+        with_bool(pl.bnw == 128, [&](auto n128) {
+          wgrad_launch<m128.value ? 128 : 64, n128.value ? 128 : 64, two.value ? 2 : 1>(grid, st, a);
+        });
+      });
+    });
   }
   if (direct_out) return;
   const WgradReduce r{part, dw, (int64_t)Cout * R * S * C / 4, pl.splits, dw_kind, false};
@@ -3096,3 +3010,4 @@ void launch_conv_wt_flip(const uint16_t* w, uint16_t* wt, int Cout, int R, int S
 }
 
 }  // namespace dpt
+

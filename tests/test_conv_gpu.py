@@ -941,8 +941,15 @@ BREG_SHAPES = SHAPES + [(s[0], s[1], s[2], s[3], s[4], 3, 1, 1) for s in HALO_SH
 ]
 
 
-@pytest.mark.parametrize("shape", BREG_SHAPES)
-def test_breg_b_operand_in_registers_matches_lds_path(cuda, shape):
+# fp16 launches its own BREG kernels: the 1x1 row and the HALO row
+BREG_F16_SHAPES = [(2, 64, 8, 8, 64, 1, 1, 0), (2, 64, 10, 10, 64, 3, 1, 1)]
+
+
+@pytest.mark.parametrize(
+    "shape,dtype",
+    [(s, torch.bfloat16) for s in BREG_SHAPES] + [(s, torch.float16) for s in BREG_F16_SHAPES],
+    ids=["shape%d" % i for i in range(len(BREG_SHAPES))] + ["f16-1x1", "f16-halo"])
+def test_breg_b_operand_in_registers_matches_lds_path(cuda, shape, dtype):
     """conv_set_breg (B operand straight from L2 into VGPRs, A double-buffered in LDS; bit 0 the
     3x3 HALO loop, bit 1 every other single-stage conv) against the default LDS-fed kernels: the
     same K-steps and k-slices in the same order, so the conv outputs are bitwise identical; the
@@ -950,11 +957,11 @@ def test_breg_b_operand_in_registers_matches_lds_path(cuda, shape):
     statistics and, for stride 1, backward-data with the BN+ReLU statistics epilogue."""
     N, C, H, W, Cout, k, s, p = shape
     C_ = ops.native()
-    x, w = _operands(cuda, N, C, H, W, Cout, k, seed=31)
+    x, w = (t.to(dtype) for t in _operands(cuda, N, C, H, W, Cout, k, seed=31))
     Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
     g = torch.Generator(device=cuda).manual_seed(32)
-    gy = torch.randn(N, Cout, Ho, Wo, device=cuda, generator=g).to(torch.bfloat16).contiguous(memory_format=CL)
-    bn_x = torch.randn(x.shape, device=cuda, generator=g).to(torch.bfloat16).contiguous(memory_format=CL)
+    gy = torch.randn(N, Cout, Ho, Wo, device=cuda, generator=g).to(dtype).contiguous(memory_format=CL)
+    bn_x = torch.randn(x.shape, device=cuda, generator=g).to(dtype).contiguous(memory_format=CL)
     bn_mean = torch.randn(C, device=cuda, generator=g)
     bn_coef = torch.randn(2 * C, device=cuda, generator=g)
     out = {}
