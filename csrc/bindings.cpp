@@ -680,6 +680,7 @@ std::vector<Tensor> attn_fwd(Tensor qkv, int64_t heads, double scale) {
   TORCH_CHECK(dpt::attn_supported(S, 64), "attn_fwd: needs S <= 256 and head dim 64");
   auto ctx = at::empty({B, S, H * 64}, qkv.options());
   auto lse = at::empty({(int64_t)B * H, dpt::attn_lse_stride(S)}, qkv.options().dtype(at::kFloat));
+  if (B * H == 0) return {ctx, lse};  // empty batch: a zero-sized grid is an invalid launch
   c10::hip::HIPGuard guard(qkv.device().index());
   dpt::launch_attn_fwd(reinterpret_cast<const uint16_t*>(qkv.data_ptr()), reinterpret_cast<uint16_t*>(ctx.data_ptr()),
                        lse.data_ptr<float>(), B, S, H, (float)scale, cur_stream(qkv));
@@ -690,12 +691,15 @@ Tensor attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, 
   check_bf16_contig(qkv, "qkv");
   check_bf16_contig(out, "out");
   check_bf16_contig(dout, "grad_output");
+  TORCH_CHECK(qkv.dim() == 3, "attn_bwd: qkv must be [B, S, 3*H*64]");
   const int B = qkv.size(0), S = qkv.size(1), H = heads;
+  TORCH_CHECK(dpt::attn_supported(S, 64), "attn_bwd: needs S <= 256 and head dim 64");
   TORCH_CHECK(out.sizes() == dout.sizes() && out.dim() == 3 && out.size(0) == B && out.size(1) == S &&
                   out.size(2) == H * 64 && qkv.size(2) == 3 * H * 64, "attn_bwd: shape mismatch");
   TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
                   lse.numel() == (int64_t)B * H * dpt::attn_lse_stride(S), "attn_bwd: bad lse");
   auto dqkv = at::empty_like(qkv);
+  if (B * H == 0) return dqkv;  // empty batch: nothing to launch
   c10::hip::HIPGuard guard(qkv.device().index());
   dpt::launch_attn_bwd(reinterpret_cast<const uint16_t*>(qkv.data_ptr()), reinterpret_cast<const uint16_t*>(out.data_ptr()),
                        reinterpret_cast<const uint16_t*>(dout.data_ptr()), lse.data_ptr<float>(),
