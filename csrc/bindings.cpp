@@ -707,6 +707,53 @@ Tensor attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, 
   return dqkv;
 }
 
+// The same op on the streaming kernels (attn_stream_kernels.hip): 1 <= S <= 4096.
+std::vector<Tensor> attn_stream_fwd(Tensor qkv, int64_t heads, double scale) {
+  check_bf16_contig(qkv, "qkv");
+  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "attn_stream_fwd: qkv must be [B, S, 3*H*64]");
+  const int B = qkv.size(0), S = qkv.size(1), H = heads;
+  TORCH_CHECK(dpt::attn_stream_supported(S, 64), "attn_stream_fwd: needs 1 <= S <= 4096 and head dim 64");
+  TORCH_CHECK((int64_t)B * H * ((S + 31) / 32) < (1LL << 31), "attn_stream_fwd: B * H * S too large for one grid");
+  auto ctx = at::empty({B, S, H * 64}, qkv.options());
+  auto lse = at::empty({(int64_t)B * H, dpt::attn_lse_stride(S)}, qkv.options().dtype(at::kFloat));
+  if (B * H == 0) return {ctx, lse};  // empty batch: a zero-sized grid is an invalid launch
+  c10::hip::HIPGuard guard(qkv.device().index());
+  dpt::launch_attn_stream_fwd(reinterpret_cast<const uint16_t*>(qkv.data_ptr()),
+                              reinterpret_cast<uint16_t*>(ctx.data_ptr()), lse.data_ptr<float>(), B, S, H,
+                              (float)scale, cur_stream(qkv));
+  return {ctx, lse};
+}
+
+Tensor attn_stream_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, double scale) {
+  check_bf16_contig(qkv, "qkv");
+  check_bf16_contig(out, "out");
+  check_bf16_contig(dout, "grad_output");
+  TORCH_CHECK(qkv.dim() == 3, "attn_stream_bwd: qkv must be [B, S, 3*H*64]");
+  const int B = qkv.size(0), S = qkv.size(1), H = heads;
+  TORCH_CHECK(dpt::attn_stream_supported(S, 64), "attn_stream_bwd: needs 1 <= S <= 4096 and head dim 64");
+  TORCH_CHECK(out.sizes() == dout.sizes() && out.dim() == 3 && out.size(0) == B && out.size(1) == S &&
+                  out.size(2) == H * 64 && qkv.size(2) == 3 * H * 64, "attn_stream_bwd: shape mismatch");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+                  lse.numel() == (int64_t)B * H * dpt::attn_lse_stride(S), "attn_stream_bwd: bad lse");
+  TORCH_CHECK((int64_t)B * H * ((S + 31) / 32) < (1LL << 31), "attn_stream_bwd: B * H * S too large for one grid");
+  auto dqkv = at::empty_like(qkv);
+  if (B * H == 0) return dqkv;  // empty batch: nothing to launch
+  auto dsum = at::empty_like(lse);  // rowsum(dO * O), written once and read by both gradient kernels
+  c10::hip::HIPGuard guard(qkv.device().index());
+  dpt::launch_attn_stream_bwd(reinterpret_cast<const uint16_t*>(qkv.data_ptr()),
+                              reinterpret_cast<const uint16_t*>(out.data_ptr()),
+                              reinterpret_cast<const uint16_t*>(dout.data_ptr()), lse.data_ptr<float>(),
+                              dsum.data_ptr<float>(), reinterpret_cast<uint16_t*>(dqkv.data_ptr()), B, S, H,
+                              (float)scale, cur_stream(qkv));
+  return dqkv;
+}
+
+std::tuple<int64_t, int64_t, int64_t> attn_stream_tiles() {
+  int qb, kc, qc;
+  dpt::attn_stream_tiles(&qb, &kc, &qc);
+  return {qb, kc, qc};
+}
+
 // 2x2 space-to-depth of a channels_last [N, C<=4, H, W] fp32/bf16 image -> channels_last bf16
 // [N, 16, H/2, W/2] (channel (a*2 + b)*4 + c)
 Tensor space_to_depth2(Tensor x, bool out_f16) {
@@ -1283,6 +1330,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_set_bwd_split", &dpt::attn_set_bwd_split, py::arg("on"));
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("grad_output"), py::arg("lse"),
         py::arg("heads"), py::arg("scale"));
+  m.def("attn_stream_fwd", &attn_stream_fwd, py::arg("qkv"), py::arg("heads"), py::arg("scale"));
+  m.def("attn_stream_bwd", &attn_stream_bwd, py::arg("qkv"), py::arg("out"), py::arg("grad_output"), py::arg("lse"),
+        py::arg("heads"), py::arg("scale"));
+  m.def("attn_stream_tiles", &attn_stream_tiles,
+        "(queries per workgroup, keys per chunk, query rows per backward chunk) of the streaming attention kernels");
   m.def("conv_set_variant", &dpt::conv_set_variant, py::arg("variant"));
   m.def("bn_set_skip_finalize", &dpt::bn_set_skip_finalize, py::arg("on"),
         "measurement only: skip every BatchNorm finalize launch (wrong values; timing upper bound)");

@@ -296,6 +296,17 @@ void launch_attn_fwd(const uint16_t* qkv, uint16_t* ctx, float* lse2, int B, int
 void launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse2,
                      uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t s);
 
+// attn_stream_kernels.hip: the same op for 1 <= S <= 4096 (head dim 64), the other side of each
+// product streamed through LDS in chunks.  Same layouts; dsum [B*H][attn_lse_stride(S)] fp32 is
+// scratch for rowsum(dO * O).  attn_stream_tiles: queries per workgroup, keys per chunk, query
+// rows per backward chunk.
+bool attn_stream_supported(int S, int Dh);
+void attn_stream_tiles(int* queries_per_wg, int* keys_per_chunk, int* query_rows_per_bwd_chunk);
+void launch_attn_stream_fwd(const uint16_t* qkv, uint16_t* ctx, float* lse2, int B, int S, int H, float scale,
+                            hipStream_t s);
+void launch_attn_stream_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse2,
+                            float* dsum, uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t s);
+
 // conv_f32_kernels.hip: channels_last fp32 convolutions on v_mfma_f32_32x32x2_f32 (exact fp32,
 // deterministic split-K).  dgrad = true: a is dy [N,Ho,Wo,Co], b the transposed weight
 // [C][R][S][Co], out dx [N,H,W,C]; otherwise a is x, b the weight [Co][R][S][C], out y.

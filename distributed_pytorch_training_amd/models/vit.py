@@ -8,7 +8,8 @@ MI355X notes
 ------------
 * Self-attention runs the fused MFMA kernels of ops/attention.py (csrc/kernels/attn_kernels.hip:
   one workgroup per (image, head), Q/K/V read straight from the QKV projection output, context
-  written straight into the out-projection input) for bf16 GPU runs; elsewhere it uses
+  written straight into the out-projection input; above 256 tokens, i.e. above 256 px,
+  csrc/kernels/attn_stream_kernels.hip with K/V streamed through LDS) for bf16 GPU runs; elsewhere it uses
   ``F.scaled_dot_product_attention`` instead of ``nn.MultiheadAttention``'s unfused path.  The parameters keep ``nn.MultiheadAttention``'s names (``in_proj_weight``,
   ``in_proj_bias``, ``out_proj.*``) so state dicts load into torchvision unchanged.
 * 197 tokens (14x14 patches + CLS): no sequence sharding is needed.
@@ -60,7 +61,8 @@ class SelfAttention(nn.Module):
             y = F.scaled_dot_product_attention(q, k, v, dropout_p=self.dropout if self.training else 0.0)
             return y.transpose(1, 2).reshape(b, s, d)
         qkv = linear16(x, shadow_param(self, "in_proj_weight", x), shadow_param(self, "in_proj_bias", x))
-        if (not self.training or self.dropout == 0.0) and fused_attn.supported(qkv, self.heads):
+        if (not self.training or self.dropout == 0.0) and (
+                fused_attn.supported(qkv, self.heads) or fused_attn.supported_streaming(qkv, self.heads)):
             return fused_attn.attention(qkv, self.heads)  # heads split/merged inside the kernels
         q, k, v = split_heads(qkv, self.heads)
         y = F.scaled_dot_product_attention(q, k, v, dropout_p=self.dropout if self.training else 0.0)
