@@ -341,7 +341,7 @@ std::vector<Tensor> conv_dgrad_bnstats(Tensor dy, Tensor w, int64_t pad, Tensor 
                                        c10::optional<Tensor> bn_y, c10::optional<Tensor> bn_res,
                                        c10::optional<Tensor> w_flipped, c10::optional<Tensor> bn_x2,
                                        c10::optional<Tensor> bn_mean2, PendingReducePtr wgrad_reduce,
-                                       c10::optional<Tensor> bn_mask) {
+                                       c10::optional<Tensor> bn_mask, bool bn_res_s2) {
   check_cl_bf16(dy, "grad_output");
   check_cl_bf16(w, "w");
   check_cl_bf16(bn_x, "bn_x");
@@ -362,9 +362,16 @@ std::vector<Tensor> conv_dgrad_bnstats(Tensor dy, Tensor w, int64_t pad, Tensor 
     check_cl_bf16(*bn_res, "bn_res");
     same_16(dy, *bn_y, "conv_dgrad_bnstats");
     same_16(dy, *bn_res, "conv_dgrad_bnstats");
-    TORCH_CHECK(bn_y->sizes() == bn_x.sizes() && bn_res->sizes() == bn_x.sizes(),
-                "conv_dgrad_bnstats: bn_y / bn_res must match bn_x");
+    TORCH_CHECK(bn_y->sizes() == bn_x.sizes(), "conv_dgrad_bnstats: bn_y must match bn_x");
+    if (bn_res_s2) {  // the compact gradient of a 1x1 / stride-2 conv over the same input
+      TORCH_CHECK(bn_res->size(0) == N && bn_res->size(1) == C && bn_res->size(2) == (H + 1) / 2 &&
+                      bn_res->size(3) == (W + 1) / 2,
+                  "conv_dgrad_bnstats: a strided bn_res must be [N, C, ceil(H/2), ceil(W/2)]");
+    } else {
+      TORCH_CHECK(bn_res->sizes() == bn_x.sizes(), "conv_dgrad_bnstats: bn_res must match bn_x");
+    }
   }
+  TORCH_CHECK(!bn_res_s2 || res, "conv_dgrad_bnstats: bn_res_s2 needs bn_y / bn_res");
   const bool pre = w_flipped.has_value() && w_flipped->defined();
   if (pre) {
     check_cl_bf16(*w_flipped, "w_flipped");
@@ -381,7 +388,7 @@ std::vector<Tensor> conv_dgrad_bnstats(Tensor dy, Tensor w, int64_t pad, Tensor 
   auto p2 = at::empty({C, mt}, dy.options().dtype(at::kFloat));
   const bool two = bn_x2.has_value() && bn_x2->defined();
   if (two) {
-    TORCH_CHECK(res, "conv_dgrad_bnstats: bn_x2 needs bn_y / bn_res");
+    TORCH_CHECK(res && !bn_res_s2, "conv_dgrad_bnstats: bn_x2 needs bn_y / bn_res, not strided");
     check_cl_bf16(*bn_x2, "bn_x2");
     same_16(dy, *bn_x2, "conv_dgrad_bnstats");
     TORCH_CHECK(bn_x2->sizes() == bn_x.sizes(), "conv_dgrad_bnstats: bn_x2 must match bn_x");
@@ -408,14 +415,14 @@ std::vector<Tensor> conv_dgrad_bnstats(Tensor dy, Tensor w, int64_t pad, Tensor 
                                  two ? reinterpret_cast<const uint16_t*>(bn_x2->data_ptr()) : nullptr,
                                  two ? f32_param(bn_mean2, C, "bn_mean2") : nullptr,
                                  two ? p3.data_ptr<float>() : nullptr, is_f16(dy),
-                                 ws.defined() ? ws.data_ptr<float>() : nullptr, mp);
+                                 ws.defined() ? ws.data_ptr<float>() : nullptr, mp, bn_res_s2);
   return {dx, p1, p2, p3};
 }
 
 // Stride-2 backward-data: dx [N, C, H, W] (channels_last) of y = conv2d(x, w, stride 2, pad).
 std::vector<Tensor> conv_dgrad_s2(Tensor dy, Tensor w, int64_t pad, int64_t H, int64_t W, c10::optional<Tensor> bn_x,
                                   c10::optional<Tensor> bn_mean, c10::optional<Tensor> bn_coef,
-                                  PendingReducePtr wgrad_reduce) {
+                                  PendingReducePtr wgrad_reduce, bool compact) {
   check_cl_bf16(dy, "grad_output");
   check_cl_bf16(w, "w");
   same_16(dy, w, "conv_dgrad_s2");
@@ -424,8 +431,13 @@ std::vector<Tensor> conv_dgrad_s2(Tensor dy, Tensor w, int64_t pad, int64_t H, i
   const int N = dy.size(0), Ho = dy.size(2), Wo = dy.size(3);
   TORCH_CHECK(Ho == (H + 2 * pad - R) / 2 + 1 && Wo == (W + 2 * pad - S) / 2 + 1, "conv_dgrad_s2: geometry mismatch");
   TORCH_CHECK((int64_t)N * H * W < (int64_t(1) << 31), "conv_dgrad_s2: too many pixels");
-  auto dx = at::empty({N, C, H, W}, dy.options().memory_format(at::MemoryFormat::ChannelsLast));
   const bool bnb = bn_x.has_value() && bn_x->defined();
+  // compact (1x1, pad 0): [N, C, Ho, Wo], the gradient of the pixels the conv read - every other
+  // element of the full dx is zero
+  TORCH_CHECK(!compact || (R == 1 && S == 1 && pad == 0 && !bnb),
+              "conv_dgrad_s2: the compact gradient needs a 1x1 kernel, pad 0 and no BN statistics");
+  auto dx = at::empty({N, C, compact ? Ho : H, compact ? Wo : W},
+                      dy.options().memory_format(at::MemoryFormat::ChannelsLast));
   c10::hip::HIPGuard guard(dy.device().index());
   const dpt::ConvS2Plan plan = dpt::conv_dgrad_s2_plan(N, (int)H, (int)W, C, Cout, R, S, (int)pad, cur_stream(dy));
   Tensor ws;
@@ -445,7 +457,7 @@ std::vector<Tensor> conv_dgrad_s2(Tensor dy, Tensor w, int64_t pad, int64_t H, i
                             bnb ? f32_param(bn_mean, C, "bn_mean") : nullptr,
                             bnb ? f32_param(bn_coef, 2 * C, "bn_coef") : nullptr,
                             bnb ? p1.data_ptr<float>() : nullptr, bnb ? p2.data_ptr<float>() : nullptr, is_f16(dy),
-                            ws.defined() ? ws.data_ptr<float>() : nullptr);
+                            ws.defined() ? ws.data_ptr<float>() : nullptr, compact);
   if (!bnb) return {dx};
   return {dx, p1, p2};
 }
@@ -1362,7 +1374,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_dgrad_bnstats", &conv_dgrad_bnstats, py::arg("grad_output"), py::arg("w"), py::arg("pad"),
         py::arg("bn_x"), py::arg("bn_mean"), py::arg("bn_coef"), py::arg("bn_y") = py::none(),
         py::arg("bn_res") = py::none(), py::arg("w_flipped") = py::none(), py::arg("bn_x2") = py::none(),
-        py::arg("bn_mean2") = py::none(), py::arg("wgrad_reduce") = nullptr, py::arg("bn_mask") = py::none());
+        py::arg("bn_mean2") = py::none(), py::arg("wgrad_reduce") = nullptr, py::arg("bn_mask") = py::none(),
+        py::arg("bn_res_s2") = false);
   m.def("conv_wt_flip_multi", &conv_wt_flip_multi, py::arg("ws"));
   m.def("conv_dgrad_preflipped", &conv_dgrad_preflipped, py::arg("grad_output"), py::arg("w_flipped"), py::arg("pad"),
         py::arg("wgrad_reduce") = nullptr);
@@ -1371,7 +1384,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("from_dz") = false);
   m.def("conv_dgrad_s2", &conv_dgrad_s2, py::arg("grad_output"), py::arg("w"), py::arg("pad"), py::arg("H"),
         py::arg("W"), py::arg("bn_x") = py::none(), py::arg("bn_mean") = py::none(), py::arg("bn_coef") = py::none(),
-        py::arg("wgrad_reduce") = nullptr);
+        py::arg("wgrad_reduce") = nullptr, py::arg("compact") = false);
   m.def("conv_dgrad_flip", &conv_dgrad_flip, py::arg("grad_output"), py::arg("w"), py::arg("pad"),
         py::arg("wgrad_reduce") = nullptr);
   py::class_<PendingReduce, PendingReducePtr>(m, "PendingWgradReduce")

@@ -132,6 +132,10 @@ struct ConvFwdArgs {
   // the same ReLU mask as 1 bit per element, [M][Cout/8] bytes written by the tail's forward
   // apply (bn_kernels.hip): read instead of bny when set - 1/16 of y's bytes
   const uint8_t* bnmask = nullptr;
+  // RS2 (with BNR): bnres is the compact gradient [N, rHo, rWo, Cout] of a 1x1 / stride-2
+  // downsample conv (rHo = ceil(Ho/2), rWo = ceil(Wo/2)): output pixel (n, h, w) adds
+  // bnres[n, h/2, w/2] when h and w are both even and +0.0 elsewhere
+  int rHo = 0, rWo = 0;
   // DGELU: the Linear's bias in the operands' 16-bit type (read instead of bn_mean when set)
   const uint16_t* bias16 = nullptr;
   // BNR with a downsample branch: the block's identity path was BN2(x2) (folded into the tail,
@@ -201,6 +205,9 @@ __device__ __attribute__((aligned(64))) uint4 g_conv_zero16[4];
 // (strided backward-data); ZSIB: also write zeros to the other three positions of each 2x2
 // cell (1x1 / stride-2 backward-data, whose other classes receive no gradient).
 // BNR2 (with BNR): the downsample-branch statistic s3 too (p.bnx2 / bn_mean2 / bp3).
+// RS2 (with BNR, not BNR2): the identity-path gradient is the compact [N, rHo, rWo, Cout] input
+// gradient of a 1x1 / stride-2 downsample conv: read at the even rows and columns, +0.0 (still
+// added) elsewhere - the full-resolution tensor, three quarters zeros, never exists.
 // F16: fp16 operands and outputs (bf16 otherwise).
 // NT: threads per block - 256 (4 waves, 2 blocks per CU) or 512 (8 waves, 2 per SIMD, one
 // 256-row block per CU: twice the MFMA work per staged byte, the large-tile regime of
@@ -217,8 +224,9 @@ __device__ __attribute__((aligned(64))) uint4 g_conv_zero16[4];
 template <int BMT, int BN, int STAGES, bool LDSEPI, bool BKN, bool STATS = true, bool BNB = false,
           bool BNR = false, bool REMAP = false, bool ZSIB = false, bool BNR2 = false, bool F16 = false,
           int NT = conv::kThreads, bool SPLIT = false, bool HALO = false, int HB = 1, bool SK = false,
-          bool DGELU = false, bool BREG = false>
+          bool DGELU = false, bool BREG = false, bool RS2 = false>
 __global__ __launch_bounds__(NT, (SK || BREG) ? 4 : 2) void conv_fwd_kernel(ConvFwdArgs p) {
+  static_assert(!RS2 || (BNR && !BNR2 && !REMAP && LDSEPI && !HALO && !BREG), "RS2 config");
   using namespace conv;
   constexpr int BM = BMT;
   constexpr int NW = NT / 64;         // waves
@@ -888,6 +896,15 @@ __global__ __launch_bounds__(NT, (SK || BREG) ? 4 : 2) void conv_fwd_kernel(Conv
       const int a = (int)(rem / (uint32_t)p.Wo), b = (int)(rem - (uint32_t)a * (uint32_t)p.Wo);
       return ((int64_t)img * p.oH + 2 * a + p.oph) * p.oW + 2 * b + p.opw;
     };
+    // RS2: element offset of output row m's entry in the compact residual (-1: an odd row or
+    // column, which the stride-2 downsample conv never read)
+    auto res_off = [&](int64_t m) -> int64_t {
+      const uint32_t mm = (uint32_t)m, hw = (uint32_t)HoWo;
+      const uint32_t img = mm / hw, rem = mm - img * hw;
+      const uint32_t h = rem / (uint32_t)p.Wo, w = rem - h * (uint32_t)p.Wo;
+      if ((h | w) & 1u) return -1;
+      return (((int64_t)img * p.rHo + (h >> 1)) * p.rWo + (w >> 1)) * p.Cout + n0 + oc * 8;
+    };
     for (int half = 0; half < (HALF ? 2 : 1); ++half) {
     if (HALF) {
       // this half's 64 rows: the waves that own them round their accumulators into the image
@@ -930,7 +947,12 @@ __global__ __launch_bounds__(NT, (SK || BREG) ? 4 : 2) void conv_fwd_kernel(Conv
               mv[q] = 0u;
               yv[q] = *reinterpret_cast<const uint4*>(p.bny + off);
             }
-            rv[q] = *reinterpret_cast<const uint4*>(p.bnres + off);
+            if (RS2) {
+              const int64_t ro = res_off(m < p.M ? m : 0);
+              rv[q] = ro >= 0 ? *reinterpret_cast<const uint4*>(p.bnres + ro) : make_uint4(0u, 0u, 0u, 0u);
+            } else {
+              rv[q] = *reinterpret_cast<const uint4*>(p.bnres + off);
+            }
             if (two) x2v[q] = *reinterpret_cast<const uint4*>(p.bnx2 + off);
             else x2v[q] = make_uint4(0u, 0u, 0u, 0u);
           }
@@ -1113,8 +1135,10 @@ __global__ __launch_bounds__(NT, (SK || BREG) ? 4 : 2) void conv_fwd_kernel(Conv
 // mask; BNR: dz = (g + res) * (y > 0) is what is stored; BNR2: s3 = sum dz*(x2 - mean2)).
 // Statistics partials: one column per 16-row slab, [C][ceil(M/16)] (conv_split_cols).
 constexpr int kSplitRows = 16;
-template <bool STATS, bool BNB, bool BNR, bool BNR2, bool REMAP, bool ZSIB, bool F16>
+// RS2: the BNR residual is a stride-2 downsample conv's compact gradient (ConvFwdArgs::rHo).
+template <bool STATS, bool BNB, bool BNR, bool BNR2, bool REMAP, bool ZSIB, bool F16, bool RS2 = false>
 __global__ __launch_bounds__(256) void conv_split_epilogue_kernel(ConvFwdArgs p) {
+  static_assert(!RS2 || (BNR && !BNR2 && !REMAP), "RS2 config");
   const int rb = blockIdx.x, cgb = blockIdx.y, cols = gridDim.x;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int oc = tid & 7, orow = (tid >> 3) & 15, half = tid >> 7;
@@ -1168,7 +1192,14 @@ __global__ __launch_bounds__(256) void conv_split_epilogue_kernel(ConvFwdArgs p)
       if (BNR) {
         if (p.bnmask != nullptr) mv = p.bnmask[off >> 3];
         else yv = *reinterpret_cast<const uint4*>(p.bny + off);
-        rv = *reinterpret_cast<const uint4*>(p.bnres + off);
+        if (RS2) {
+          const int64_t hw = (int64_t)p.Ho * p.Wo, img = grow / hw, rem = grow - img * hw;
+          const int h = (int)(rem / p.Wo), w = (int)(rem - (int64_t)h * p.Wo);
+          if (((h | w) & 1) == 0)
+            rv = *reinterpret_cast<const uint4*>(p.bnres + ((img * p.rHo + (h >> 1)) * p.rWo + (w >> 1)) * p.Cout + c0);
+        } else {
+          rv = *reinterpret_cast<const uint4*>(p.bnres + off);
+        }
         if (two) x2v = *reinterpret_cast<const uint4*>(p.bnx2 + off);
       }
       const uint32_t xu[4] = {xv.x, xv.y, xv.z, xv.w}, yu[4] = {yv.x, yv.y, yv.z, yv.w};
@@ -2265,7 +2296,7 @@ void conv_set_wgrad_stages(int mode) { g_wgrad_stages = mode; }
 enum : unsigned {
   kLdsEpi = 1u << 0, kBkn = 1u << 1, kStats = 1u << 2, kBnb = 1u << 3, kBnr = 1u << 4, kRemap = 1u << 5,
   kZsib = 1u << 6, kBnr2 = 1u << 7, kF16 = 1u << 8, kSplit = 1u << 9, kHalo = 1u << 10, kSk = 1u << 11,
-  kDgelu = 1u << 12, kBreg = 1u << 13, kDir = 1u << 14,
+  kDgelu = 1u << 12, kBreg = 1u << 13, kDir = 1u << 14, kRs2 = 1u << 15,
 };
 static constexpr bool has(unsigned flags, unsigned f) { return (flags & f) != 0; }
 static constexpr unsigned opt(bool on, unsigned f) { return on ? f : 0u; }
@@ -2285,14 +2316,15 @@ template <int BMT, int BN, int STAGES, unsigned F, int NT = conv::kThreads, int 
 static void launch_fwd_kernel(dim3 grid, hipStream_t s, const ConvFwdArgs& a) {
   hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, STAGES, has(F, kLdsEpi), has(F, kBkn), has(F, kStats), has(F, kBnb),
                                       has(F, kBnr), has(F, kRemap), has(F, kZsib), has(F, kBnr2), has(F, kF16), NT,
-                                      has(F, kSplit), has(F, kHalo), HB, has(F, kSk), has(F, kDgelu), has(F, kBreg)>),
+                                      has(F, kSplit), has(F, kHalo), HB, has(F, kSk), has(F, kDgelu), has(F, kBreg),
+                                      has(F, kRs2)>),
                      grid, dim3(NT), 0, s, a);
 }
 
 template <unsigned F>
 static void launch_split_epilogue_kernel(dim3 grid, hipStream_t s, const ConvFwdArgs& a) {
   hipLaunchKernelGGL((conv_split_epilogue_kernel<has(F, kStats), has(F, kBnb), has(F, kBnr), has(F, kBnr2),
-                                                 has(F, kRemap), has(F, kZsib), has(F, kF16)>),
+                                                 has(F, kRemap), has(F, kZsib), has(F, kF16), has(F, kRs2)>),
                      grid, dim3(256), 0, s, a);
 }
 
@@ -2465,7 +2497,7 @@ static void fwd_launch(dim3 grid, hipStream_t s, const ConvFwdArgs& a0) {
   ConvFwdArgs a = a0;
   if constexpr (NT == conv::kThreads) grid.x += (unsigned)take_attached_reduce(a.red);
   conv_check_offsets(a, has(F, kBkn));
-  if constexpr (kProd && !has(F, kBkn | kRemap)) {
+  if constexpr (kProd && !has(F, kBkn | kRemap | kRs2)) {  // (kRs2: the plain and stream-K tiles only)
     const bool halo = halo_ok(a);
     // B operand in registers (conv_set_breg: bit 0 the 3x3 HALO convs, bit 1 the others)
     if ((g_conv_breg & (halo ? 1 : 2)) && a.n_tiles * BN == a.Cout) {
@@ -2697,28 +2729,35 @@ void launch_conv_dgrad_bnstats(const uint16_t* dy, const uint16_t* wt, uint16_t*
                                int C, int R, int S, int pad, const uint16_t* bnx, const float* bn_mean,
                                const float* bn_coef, float* bp1, float* bp2, hipStream_t s,
                                const uint16_t* bny, const uint16_t* bnres, const uint16_t* bnx2,
-                               const float* bn_mean2, float* bp3, bool f16, float* ws, const uint8_t* bnmask) {
+                               const float* bn_mean2, float* bp3, bool f16, float* ws, const uint8_t* bnmask,
+                               bool res_s2) {
   const int padb = R - 1 - pad;
   ConvFwdArgs a = conv_args(dy, wt, dx, f16, N, Ho, Wo, Cout, C, R, S, 1, padb, Ho + 2 * padb - R + 1,
                             Wo + 2 * padb - S + 1);
   a.bnx = bnx; a.bn_mean = bn_mean; a.bn_coef = bn_coef; a.bp1 = bp1; a.bp2 = bp2;
   a.bny = bny; a.bnres = bnres; a.bnmask = bnmask;
   a.bnx2 = bnx2; a.bn_mean2 = bn_mean2; a.bp3 = bp3;
+  a.rHo = (a.Ho + 1) / 2; a.rWo = (a.Wo + 1) / 2;
   const auto run = [&](auto epi) {
     constexpr unsigned E = decltype(epi)::value;
     a.bp_ld = conv_split_cols(a.M);  // split: one partial column per 16-row slab
     if (maybe_split<E>(a, ws, s)) return;
     a.bp_ld = a.m_tiles;
-    const int cv = fwd_variant();
-    if (!f16 && (cv == 0 || (cv >= 9 && cv <= 13))) {
-      // 8-wave tiles (conv_big_auto, or a forced variant): N = C, K = Cout*R*S
-      const int vb = cv ? cv : conv_big_auto(a.M, C, (int64_t)Cout * R * S, R * S);
-      if (vb && conv_fwd_big<E>(vb, a, s)) return;
+    if constexpr (!has(E, kRs2)) {  // (the strided residual: the 4-wave tile only)
+      const int cv = fwd_variant();
+      if (!f16 && (cv == 0 || (cv >= 9 && cv <= 13))) {
+        // 8-wave tiles (conv_big_auto, or a forced variant): N = C, K = Cout*R*S
+        const int vb = cv ? cv : conv_big_auto(a.M, C, (int64_t)Cout * R * S, R * S);
+        if (vb && conv_fwd_big<E>(vb, a, s)) return;
+      }
     }
     fwd_launch_default<E>(a, s);
   };
   const bool res = bny != nullptr;
-  if (res && bnx2 != nullptr) run(Opts<kBnb | kBnr | kBnr2>{});
+  if (res_s2 && (!res || bnx2 != nullptr))
+    throw std::runtime_error("conv_dgrad_bnstats: a strided residual needs bny / bnres and no bnx2");
+  if (res_s2) run(Opts<kBnb | kBnr | kRs2>{});
+  else if (res && bnx2 != nullptr) run(Opts<kBnb | kBnr | kBnr2>{});
   else if (res) run(Opts<kBnb | kBnr>{});
   else run(Opts<kBnb>{});
 }
@@ -2816,7 +2855,8 @@ int conv_dgrad_s2_chunks(int N, int H, int W, int R, int S, int pad) {
 
 void launch_conv_dgrad_s2(const uint16_t* dy, const uint16_t* w, uint16_t* dx, int N, int Ho, int Wo, int Cout,
                           int C, int R, int S, int pad, int H, int W, hipStream_t s, const uint16_t* bnx,
-                          const float* bn_mean, const float* bn_coef, float* bp1, float* bp2, bool f16, float* ws) {
+                          const float* bn_mean, const float* bn_coef, float* bp1, float* bp2, bool f16, float* ws,
+                          bool compact) {
   const bool bnb = bnx != nullptr;
   // with a workspace the classes may split (the caller sized ws and bp_ld by conv_dgrad_s2_plan)
   const int bp_ld = bnb ? (ws ? conv_dgrad_s2_plan(N, H, W, C, Cout, R, S, pad, s).chunks
@@ -2825,6 +2865,10 @@ void launch_conv_dgrad_s2(const uint16_t* dy, const uint16_t* w, uint16_t* dx, i
   int bp_off = 0;
   S2Class cl[4];
   const int ncl = s2_classes(H, W, R, S, pad, cl);
+  // compact (1x1 kernels): dx is [N, ceil(H/2), ceil(W/2), C], the one non-empty class as it comes
+  // out of the GEMM - the same launch without the scatter (REMAP) and the zeros (ZSIB)
+  if (compact && (bnb || ncl != 1 || !cl[0].zsib))
+    throw std::runtime_error("conv_dgrad_s2: the compact gradient needs a 1x1 kernel and no BN statistics");
   for (int ci = 0; ci < ncl; ++ci) {
     const S2Class& k = cl[ci];
     ConvFwdArgs a = conv_args(dy, w, dx, f16, N, Ho, Wo, Cout, C, k.Rc, k.Sc, 1, k.pad, k.Ha, k.Wa);
@@ -2838,7 +2882,7 @@ void launch_conv_dgrad_s2(const uint16_t* dy, const uint16_t* w, uint16_t* dx, i
     // in the models here: BNB and ZSIB are not combined
     if (bnb && k.zsib) throw std::runtime_error("conv_dgrad_s2: BN statistics with zero-filled classes unsupported");
     const auto run = [&](auto epi) {
-      constexpr unsigned F = kBkn | kRemap | decltype(epi)::value;
+      constexpr unsigned F = kBkn | decltype(epi)::value;
       if (maybe_split<F>(a, ws, s)) {
         bp_off += conv_split_cols(a.M);
         return;
@@ -2846,9 +2890,10 @@ void launch_conv_dgrad_s2(const uint16_t* dy, const uint16_t* w, uint16_t* dx, i
       bp_off += a.m_tiles;
       fwd_launch_default<F>(a, s);
     };
-    if (bnb) run(Opts<kBnb>{});
-    else if (k.zsib) run(Opts<kZsib>{});
-    else run(Opts<0u>{});
+    if (compact) run(Opts<0u>{});
+    else if (bnb) run(Opts<kRemap | kBnb>{});
+    else if (k.zsib) run(Opts<kRemap | kZsib>{});
+    else run(Opts<kRemap>{});
   }
 }
 

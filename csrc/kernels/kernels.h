@@ -249,7 +249,10 @@ void launch_conv_dgrad_bnstats(const uint16_t* dy, const uint16_t* wt, uint16_t*
                                const uint16_t* bny = nullptr, const uint16_t* bnres = nullptr,
                                const uint16_t* bnx2 = nullptr, const float* bn_mean2 = nullptr,
                                float* bp3 = nullptr, bool f16 = false, float* ws = nullptr,
-                               const uint8_t* bnmask = nullptr);
+                               const uint8_t* bnmask = nullptr, bool res_s2 = false);
+// res_s2 (with bny / bnres, not with bnx2): bnres is [N, ceil(Ho'/2), ceil(Wo'/2), C], the compact
+// gradient of a 1x1 / stride-2 conv over the same [N, Ho', Wo', C] input: added at the even
+// rows and columns, +0.0 elsewhere
 // many weights flipped/transposed (wt[ci][R-1-r][S-1-s][co] = w[co][r][s][ci]) in one launch
 constexpr int kWtFlipMax = 64;
 struct WtFlipBatch {
@@ -269,7 +272,9 @@ ConvS2Plan conv_dgrad_s2_plan(int N, int H, int W, int C, int Cout, int R, int S
 void launch_conv_dgrad_s2(const uint16_t* dy, const uint16_t* w, uint16_t* dx, int N, int Ho, int Wo, int Cout,
                           int C, int R, int S, int pad, int H, int W, hipStream_t s, const uint16_t* bnx = nullptr,
                           const float* bn_mean = nullptr, const float* bn_coef = nullptr, float* bp1 = nullptr,
-                          float* bp2 = nullptr, bool f16 = false, float* ws = nullptr);
+                          float* bp2 = nullptr, bool f16 = false, float* ws = nullptr, bool compact = false);
+// compact (1x1 kernels, no BN statistics): dx is [N, ceil(H/2), ceil(W/2), C] - the gradient at
+// the even rows and columns, the only ones such a conv read; the rest of the full dx is zero
 // [C][chunks] partial columns the BN-statistics variant of launch_conv_dgrad_s2 writes
 int conv_dgrad_s2_chunks(int N, int H, int W, int R, int S, int pad);
 // stride-1 backward-data straight from the KRSC weight w [Cout,R,S,C]: dy [N,Ho,Wo,Cout] -> dx [N,Ho,Wo,C]

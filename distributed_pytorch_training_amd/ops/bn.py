@@ -24,7 +24,7 @@ import torch
 import os
 
 from . import native, native_available
-from .conv import MASKED_NO_RES, take_bnb_partials
+from .conv import COMPACT_RES, MASKED_NO_RES, take_bnb_partials
 
 # Block-tail BN+add+ReLU backward statistics in the consuming conv's dgrad epilogue (see _bwd)
 BNR_FUSE = os.environ.get("DPT_BNR_FUSE", "1") != "0"
@@ -134,9 +134,12 @@ def _bwd(ctx, dy, dy2):
             return (dx, dy if want_dz else None, dg if want_params else None, db if want_params else None)
     if dy2 is None and ctx.relu and ctx.has_res:
         part = take_bnb_partials(dy)
-        if part is not None and part[2] == MASKED_NO_RES:
+        if part is not None and part[2] in (MASKED_NO_RES, COMPACT_RES):
             # the last block tail: the average-pool backward formed dz = dy * (y > 0) and summed
-            # the statistics (ops/pool.py gap_bwd_bnr); dz is also the residual gradient
+            # the statistics (ops/pool.py gap_bwd_bnr); dz is also the residual gradient.
+            # COMPACT_RES: the identity alias fed a 1x1 / stride-2 downsample conv, which handed its
+            # compact input gradient to the conv-path consumer and returned None to autograd
+            # (ops/conv.py S2_COMPACT_DRES): dy is the whole masked gradient, nothing is missing
             dx, dg, db = native().bn_bwd_partials(dy, x, weight, mean, invstd, None, part[0], part[1],
                                                   bool(want_params), True)
             if ctx.res_slot is not None:

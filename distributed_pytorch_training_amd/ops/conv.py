@@ -7,7 +7,9 @@ forward   implicit-GEMM conv; with ``bn_stats`` its epilogue also emits the per-
           from the output tensor's ``_dpt_bn_partials`` attribute).
 backward  input gradient: the same kernel on dy reading the weight as [co][ci] with flipped taps
           through transposing LDS reads (stride 1), or, stride 2, four parity-class convs whose
-          outputs are scattered onto the even/odd rows and columns of dx; weight gradient: split-K MFMA kernel
+          outputs are scattered onto the even/odd rows and columns of dx (a 1x1 downsample conv on a
+          block tail's identity alias keeps its one non-empty class compact instead and hands it to
+          the tail's conv-path consumer, S2_COMPACT_DRES); weight gradient: split-K MFMA kernel
           with transposing LDS reads, bf16 (the shadow weight's dtype).
 
 Replaces the reference's cuDNN convolutions (reference
@@ -40,6 +42,11 @@ _BNB_PARTIALS = {}
 _GEN = [0]
 # Stride-2 backward-data on the MFMA kernels (four parity-class convs); 0 = MIOpen
 S2_DGRAD = os.environ.get("DPT_S2_DGRAD", "1") != "0"
+# A 1x1 / stride-2 downsample conv fed by a block tail's identity alias hands its input gradient
+# to the tail's conv-path consumer compactly, [N, C, ceil(H/2), ceil(W/2)] (the pixels it read),
+# and returns None to autograd: the full-resolution tensor, three quarters explicit zeros, is
+# neither written nor read back by the consumer's BNR epilogue.  0 = the full tensor.
+S2_COMPACT_DRES = os.environ.get("DPT_S2_COMPACT_DRES", "1") != "0"
 # Backward-weight before backward-data, its split-K reduce run by extra blocks in the
 # backward-data launch's tail (conv_wgrad_deferred / wgrad_reduce=): no reduce launch of its own
 WGRAD_REDUCE_FUSE = os.environ.get("DPT_WGRAD_REDUCE_FUSE", "1") != "0"
@@ -127,13 +134,25 @@ def _backward(ctx, dy):
         src = ctx.bn_src if (s == 1 and BN_BWD_FUSE) else None
         dres = None
         wt = _flipped(w) if s == 1 else None
+        slot = ctx.bn_src[2] if (ctx.bn_src is not None and isinstance(ctx.bn_src[2], dict)) else None
+        compact = False
+        if slot is not None:
+            # from here on the tail's downsample conv must not leave a compact gradient behind
+            slot.pop("fold_s2", None)
+            # it ran first, left its compact gradient in the slot and returned None to autograd
+            # (S2_COMPACT_DRES): fold it below, or nobody accounts for it
+            compact = bool(slot.pop("dres_s2", False))
+            if compact and not (src is not None and len(src) == 3 and _is_compact_of(slot.get("dres"), x)):
+                raise RuntimeError("fused block-tail backward: a downsample conv handed over a compact "
+                                   "identity-path gradient that this conv's backward-data cannot fold")
         if src is not None and not isinstance(src[2], dict):  # BN+ReLU: (x, mean, coef)
             bn_x, bn_mean, bn_coef = src
             dx, p1, p2, _ = native().conv_dgrad_bnstats(dy, w, p, bn_x, bn_mean, bn_coef, w_flipped=wt,
                                                         wgrad_reduce=red)
             _put_bnb(dx, p1, p2, None, None)
             variant = "bnrelu-stats"
-        elif src is not None and _dres_ok(dres := src[2].pop("dres", None), x):  # (x, mean, slot)
+        elif (src is not None and _dres_ok(dres := src[2].pop("dres", None), x)   # (x, mean, slot)
+              and (compact or dres.shape == x.shape)):
             # block-tail BN+add+ReLU (ops/bn.py pair outputs): the next block's tail already
             # produced the identity-path gradient dres; dx becomes the tail's masked total
             # gradient, the conv's input x is the tail's output y (the ReLU mask)
@@ -143,16 +162,25 @@ def _backward(ctx, dy):
             x2, mean2 = (src[3], src[4]) if len(src) > 3 else (None, None)
             # the tail's 1-bit ReLU mask (ops/bn.py) is read instead of its output x when present
             dx, p1, p2, p3 = native().conv_dgrad_bnstats(dy, w, p, bn_x, bn_mean, None, x, dres, wt, x2, mean2,
-                                                         wgrad_reduce=red, bn_mask=src[2].get("mask"))
-            _put_bnb(dx, p1, p2, dres.data_ptr(), p3 if x2 is not None else None)
-            variant = "tail+ds-stats" if x2 is not None else "tail-stats"
+                                                         wgrad_reduce=red, bn_mask=src[2].get("mask"),
+                                                         bn_res_s2=compact)
+            _put_bnb(dx, p1, p2, COMPACT_RES if compact else dres.data_ptr(), p3 if x2 is not None else None)
+            variant = "tail-stats-s2res" if compact else "tail+ds-stats" if x2 is not None else "tail-stats"
         elif s == 1:
             dx = (native().conv_dgrad_flip(dy, w, p, wgrad_reduce=red)[0] if wt is None
                   else native().conv_dgrad_preflipped(dy, wt, p, wgrad_reduce=red))
             variant = "plain"
         elif s == 2 and S2_DGRAD and x.dim() == 4:
             src = ctx.bn_src if BN_BWD_FUSE else None
-            if src is not None and not isinstance(src[2], dict) and w.shape[2] > 1:
+            rs = ctx.res_slot
+            if (ctx.compact_dres and S2_COMPACT_DRES and BN_BWD_FUSE and rs is not None and rs.get("fold_s2")
+                    and "dres" not in rs):
+                # the conv-path consumer of the tail has not run yet and will fold (see conv2d)
+                rs["dres"] = native().conv_dgrad_s2(dy, w, p, x.shape[2], x.shape[3], wgrad_reduce=red,
+                                                    compact=True)[0]
+                rs["dres_s2"] = True
+                variant = "s2-compact"
+            elif src is not None and not isinstance(src[2], dict) and w.shape[2] > 1:
                 # BN+ReLU input: its backward statistics from the parity-class epilogues too
                 dx, p1, p2 = native().conv_dgrad_s2(dy, w, p, x.shape[2], x.shape[3], src[0], src[1], src[2],
                                                     wgrad_reduce=red)
@@ -168,6 +196,8 @@ def _backward(ctx, dy):
         native().conv_reduce_flush(red)   # no native backward-data launch took it
     if variant is not None:
         _note("dgrad", x, w, s, p, variant + ("+reduce" if red is not None else ""), e0)
+    if variant == "s2-compact":
+        return None, dw   # the gradient went to the consumer through the slot, not through autograd
     if dx is not None and ctx.res_slot is not None:
         # x is the identity alias of a fused block tail and this conv its downsample: hand the
         # identity-path gradient to the tail's conv-path consumer (see ops/bn.py)
@@ -221,41 +251,52 @@ def _flipped(w: torch.Tensor):
     return wt
 
 
+def _is_compact_of(dres, x) -> bool:
+    """dres has the shape of a 1x1 / stride-2 conv's compact input gradient for the input x."""
+    n, c, h, w = x.shape
+    return (dres is not None and dres.dtype == x.dtype and dres.is_contiguous(memory_format=_CL)
+            and tuple(dres.shape) == (n, c, (h + 1) // 2, (w + 1) // 2))
+
+
 def _dres_ok(dres, x) -> bool:
-    return (dres is not None and dres.dtype == x.dtype and dres.shape == x.shape
+    """dres can be folded into the backward-data of the conv whose input is x: x's dtype and layout,
+    x's shape or its compact form (the caller knows which from the slot's ``dres_s2``)."""
+    return (dres is not None and dres.dtype == x.dtype and (dres.shape == x.shape or _is_compact_of(dres, x))
             and dres.is_contiguous(memory_format=_CL))
 
 
 class _Conv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, stride: int, pad: int, out_hw, bn_src, res_slot):
+    def forward(ctx, x, w, stride: int, pad: int, out_hw, bn_src, res_slot, compact_dres):
         e0 = _mark()
         y = native().conv_fwd(x, w, stride, pad, False, *out_hw)[0]
         _note("fwd", x, w, stride, pad, "plain", e0, out_hw)
         ctx.save_for_backward(x, w)
         ctx.stride, ctx.pad, ctx.bn_src, ctx.res_slot = stride, pad, bn_src, res_slot
+        ctx.compact_dres = compact_dres
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        return _backward(ctx, dy) + (None,) * 5
+        return _backward(ctx, dy) + (None,) * 6
 
 
 class _ConvStats(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, stride: int, pad: int, out_hw, bn_src, res_slot):
+    def forward(ctx, x, w, stride: int, pad: int, out_hw, bn_src, res_slot, compact_dres):
         e0 = _mark()
         y, ps, pq = native().conv_fwd(x, w, stride, pad, True, *out_hw)
         _note("fwd", x, w, stride, pad, "stats", e0, out_hw)
         ctx.save_for_backward(x, w)
         ctx.stride, ctx.pad, ctx.bn_src, ctx.res_slot = stride, pad, bn_src, res_slot
+        ctx.compact_dres = compact_dres
         ctx.mark_non_differentiable(ps, pq)
         ctx.set_materialize_grads(False)  # no zero-filled gradients for the statistics outputs
         return y, ps, pq
 
     @staticmethod
     def backward(ctx, dy, _dps, _dpq):
-        return _backward(ctx, dy) + (None,) * 5
+        return _backward(ctx, dy) + (None,) * 6
 
 
 def conv2d(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, bn_stats: bool = False,
@@ -270,9 +311,18 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, bn_stats: bo
     bn_src = x.__dict__.get("_dpt_bn_src")
     # x is the identity alias of a fused block tail (this conv is a downsample)
     res_slot = x.__dict__.get("_dpt_res_slot")
+    one_by_one = w.shape[2] == 1 and w.shape[3] == 1
+    if (int(stride) == 1 and one_by_one and BN_BWD_FUSE and bn_src is not None and len(bn_src) == 3
+            and isinstance(bn_src[2], dict)):
+        # a 1x1 / stride-1 conv on a block tail's conv-path output: its backward-data folds the
+        # identity-path gradient (BNR), a stride-2 downsample conv's compact one included - told to
+        # that conv (which runs after this one, models/resnet.py) through the shared slot
+        bn_src[2]["fold_s2"] = True
+    compact_dres = bool(S2_COMPACT_DRES and S2_DGRAD and int(stride) == 2 and one_by_one and int(pad) == 0
+                        and tuple(out_hw) == (0, 0) and res_slot is not None and res_slot.get("fold_s2"))
     if not bn_stats:
-        return _Conv.apply(x, w, int(stride), int(pad), tuple(out_hw), bn_src, res_slot)
-    y, ps, pq = _ConvStats.apply(x, w, int(stride), int(pad), tuple(out_hw), bn_src, res_slot)
+        return _Conv.apply(x, w, int(stride), int(pad), tuple(out_hw), bn_src, res_slot, compact_dres)
+    y, ps, pq = _ConvStats.apply(x, w, int(stride), int(pad), tuple(out_hw), bn_src, res_slot, compact_dres)
     y._dpt_bn_partials = (ps, pq)
     return y
 
@@ -280,6 +330,9 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, bn_stats: bo
 # dres_ptr of an entry whose gradient is a block tail's already-masked gradient with no
 # identity-path gradient folded in (the last tail, whose output only fed the average pool)
 MASKED_NO_RES = -1
+# dres_ptr of an entry whose gradient is a block tail's masked gradient with a downsample conv's
+# compact identity-path gradient folded in (S2_COMPACT_DRES): autograd delivers no second gradient
+COMPACT_RES = -2
 
 
 def register_bnb_partials(dx: torch.Tensor, p1: torch.Tensor, p2: torch.Tensor, masked: bool = False) -> None:
