@@ -832,15 +832,25 @@ std::vector<Tensor> bn_fwd_train(Tensor x, c10::optional<Tensor> residual, c10::
   return {y, mean, invstd, coef};
 }
 
+// The output of an apply pass: a new tensor like x, or the caller's y_out (x's shape, dtype, layout).
+static Tensor apply_out(const c10::optional<Tensor>& y_out, const Tensor& x, const char* who) {
+  if (!y_out.has_value() || !y_out->defined()) return at::empty_like(x);
+  TORCH_CHECK(y_out->device() == x.device() && y_out->scalar_type() == x.scalar_type() && y_out->sizes() == x.sizes() &&
+                  y_out->strides() == x.strides(),
+              who, ": y_out must match x in device, dtype, shape and layout");
+  return *y_out;
+}
+
 // y = relu(x*a + b + x2*a2 + b2), coef = [a | b], coef2 = [a2 | b2] (bn_fwd_train coefficients)
-Tensor bn_apply_aff(Tensor x, Tensor x2, Tensor coef, Tensor coef2, c10::optional<Tensor> mask_out) {
+Tensor bn_apply_aff(Tensor x, Tensor x2, Tensor coef, Tensor coef2, c10::optional<Tensor> mask_out,
+                    c10::optional<Tensor> y_out) {
   auto [M, C] = bn_rows(x, "x");
   TORCH_CHECK(dpt::bn_supported(C), "fused BN: unsupported channel count ", C);
   TORCH_CHECK(x2.sizes() == x.sizes() && x2.scalar_type() == x.scalar_type(), "bn_apply_aff: x2 mismatch");
   bn_rows(x2, "x2");
   const float* a = f32_param(coef, 2 * C, "coef");
   const float* a2 = f32_param(coef2, 2 * C, "coef2");
-  auto y = at::empty_like(x);
+  auto y = apply_out(y_out, x, "bn_apply_aff");
   c10::hip::HIPGuard guard(x.device().index());
   uint8_t* mp = relu_mask_ptr(mask_out, M, C, x, "bn_apply_aff");
   dpt::launch_bn_apply_aff(bn_dtype(x), x.data_ptr(), x2.data_ptr(), y.data_ptr(), M, C, a, a + C, a2, a2 + C,
@@ -878,7 +888,10 @@ std::vector<Tensor> bn2_bwd_partials(Tensor dz, Tensor x, Tensor x2, c10::option
   return {dx, dx2, dg, db, dg2, db2};
 }
 
-Tensor bn_apply(Tensor x, c10::optional<Tensor> residual, Tensor a, Tensor b, bool relu) {
+// mask_out (relu + residual only): the 1-bit ReLU mask of y.  y_out: write into this tensor (x's
+// shape, dtype and layout) instead of a new one.
+Tensor bn_apply(Tensor x, c10::optional<Tensor> residual, Tensor a, Tensor b, bool relu,
+                c10::optional<Tensor> mask_out, c10::optional<Tensor> y_out) {
   auto [M, C] = bn_rows(x, "x");
   TORCH_CHECK(dpt::bn_supported(C), "fused BN: unsupported channel count ", C);
   const void* rp = nullptr;
@@ -887,11 +900,52 @@ Tensor bn_apply(Tensor x, c10::optional<Tensor> residual, Tensor a, Tensor b, bo
     bn_rows(*residual, "residual");
     rp = residual->data_ptr();
   }
-  auto y = at::empty_like(x);
+  auto y = apply_out(y_out, x, "bn_apply");
+  uint8_t* mp = relu_mask_ptr(mask_out, M, C, x, "bn_apply");
+  TORCH_CHECK(mp == nullptr || (relu && rp != nullptr), "bn_apply: mask_out needs relu + residual");
   c10::hip::HIPGuard guard(x.device().index());
   dpt::launch_bn_apply(bn_dtype(x), x.data_ptr(), rp, y.data_ptr(), M, C, f32_param(a, C, "a"),
-                       f32_param(b, C, "b"), relu, cur_stream(x));
+                       f32_param(b, C, "b"), relu, cur_stream(x), mp);
   return y;
+}
+
+// Block-tail apply fused into the next block's 1x1 / stride-1 forward conv (tail_conv1_kernels.hip):
+// y_out = relu(x3*a + b + r) (coef2 None) or relu(x3*a + b + r*a2 + b2), mask_out its 1-bit ReLU
+// mask, and {x1, psum, psq} = conv_fwd(y_out, w, 1, 0, want_stats = true), all bit for bit.
+// Refuses (raises) what the kernel does not cover; nothing is written then.
+std::vector<Tensor> conv1x1_tail_fwd(Tensor x3, Tensor r, Tensor coef, c10::optional<Tensor> coef2, Tensor w,
+                                     Tensor y_out, Tensor mask_out, int64_t stride, int64_t pad) {
+  check_cl_bf16(x3, "x3");
+  check_cl_bf16(r, "residual");
+  check_cl_bf16(w, "w");
+  check_cl_bf16(y_out, "y_out");
+  same_16(x3, w, "conv1x1_tail_fwd");
+  TORCH_CHECK(r.sizes() == x3.sizes() && r.scalar_type() == x3.scalar_type(), "conv1x1_tail_fwd: residual mismatch");
+  TORCH_CHECK(y_out.sizes() == x3.sizes() && y_out.scalar_type() == x3.scalar_type(),
+              "conv1x1_tail_fwd: y_out mismatch");
+  const int N = x3.size(0), C = x3.size(1), H = x3.size(2), W = x3.size(3);
+  const int64_t M = (int64_t)N * H * W;
+  const int Cout = w.size(0);
+  TORCH_CHECK(w.size(1) == C, "conv1x1_tail_fwd: channel mismatch");
+  TORCH_CHECK(w.size(2) == 1 && w.size(3) == 1 && stride == 1 && pad == 0,
+              "conv1x1_tail_fwd: a 1x1 / stride-1 / unpadded conv only");
+  const char* why = dpt::tail_conv1_refusal(M, C, Cout);
+  TORCH_CHECK(why == nullptr, "conv1x1_tail_fwd: ", why ? why : "");
+  const float* a = f32_param(coef, 2 * C, "coef");
+  const float* a2 = f32_param(coef2, 2 * C, "coef2");
+  uint8_t* mp = relu_mask_ptr(mask_out, M, C, x3, "conv1x1_tail_fwd");
+  TORCH_CHECK(mp != nullptr, "conv1x1_tail_fwd: mask_out is required");
+  auto x1 = at::empty({N, Cout, H, W}, x3.options().memory_format(at::MemoryFormat::ChannelsLast));
+  const int64_t mt = dpt::conv_m_tiles(M);
+  auto ps = at::empty({Cout, mt}, x3.options().dtype(at::kFloat));
+  auto pq = at::empty({Cout, mt}, x3.options().dtype(at::kFloat));
+  c10::hip::HIPGuard guard(x3.device().index());
+  dpt::launch_tail_conv1_fwd(is_f16(x3), reinterpret_cast<const uint16_t*>(x3.data_ptr()),
+                             reinterpret_cast<const uint16_t*>(r.data_ptr()), a, a2,
+                             reinterpret_cast<const uint16_t*>(w.data_ptr()), reinterpret_cast<uint16_t*>(y_out.data_ptr()),
+                             mp, reinterpret_cast<uint16_t*>(x1.data_ptr()), ps.data_ptr<float>(), pq.data_ptr<float>(), M,
+                             C, Cout, cur_stream(x3));
+  return {x1, ps, pq};
 }
 
 // Returns {dx, dgamma, dbeta, dz}.  dy2: gradient of the second (aliased) output, if the
@@ -1297,9 +1351,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("running_mean"), py::arg("running_var"), py::arg("num_batches"), py::arg("momentum"), py::arg("eps"),
         py::arg("relu"), py::arg("psum") = py::none(), py::arg("psq") = py::none(), py::arg("apply") = true,
         py::arg("mask_out") = py::none());
-  m.def("bn_apply", &bn_apply, py::arg("x"), py::arg("residual"), py::arg("a"), py::arg("b"), py::arg("relu"));
+  m.def("bn_apply", &bn_apply, py::arg("x"), py::arg("residual"), py::arg("a"), py::arg("b"), py::arg("relu"),
+        py::arg("mask_out") = py::none(), py::arg("y_out") = py::none());
   m.def("bn_apply_aff", &bn_apply_aff, py::arg("x"), py::arg("x2"), py::arg("coef"), py::arg("coef2"),
-        py::arg("mask_out") = py::none());
+        py::arg("mask_out") = py::none(), py::arg("y_out") = py::none());
+  m.def("conv1x1_tail_fwd", &conv1x1_tail_fwd, py::arg("x3"), py::arg("res_or_x2"), py::arg("coef"), py::arg("coef2"),
+        py::arg("w"), py::arg("y_out"), py::arg("mask_out"), py::arg("stride") = 1, py::arg("pad") = 0);
+  m.def("conv1x1_tail_refusal", [](int64_t M, int64_t Cin, int64_t Cout) -> py::object {
+          const char* why = dpt::tail_conv1_refusal(M, Cin, Cout);
+          return why ? py::object(py::str(why)) : py::object(py::none());
+        }, py::arg("M"), py::arg("Cin"), py::arg("Cout"),
+        "why conv1x1_tail_fwd refuses this shape (None: it takes it)");
   m.def("bn2_bwd_partials", &bn2_bwd_partials, py::arg("dz"), py::arg("x"), py::arg("x2"), py::arg("weight"),
         py::arg("weight2"), py::arg("mean"), py::arg("invstd"), py::arg("mean2"), py::arg("invstd2"), py::arg("p1"),
         py::arg("p2"), py::arg("p3"), py::arg("want_dparams"));

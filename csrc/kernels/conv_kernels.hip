@@ -71,31 +71,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 }  // namespace conv
 
-// 16-bit element type of a conv (F16 = false: bf16, true: fp16).  Operands travel as raw 16-bit
-// data (glds, LDS, fragments); only the MFMA and the fp32 <-> 16-bit conversions differ.
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-
-template <bool F16>
-__device__ __forceinline__ f32x16_t cmfma(bf16x8_t a, bf16x8_t b, f32x16_t c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c,
-                                                  0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-// two fp32 -> a packed 16-bit pair (round to nearest even: v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32)
-template <bool F16>
-__device__ __forceinline__ uint32_t cpack(f32x2_t v) {
-  if constexpr (F16) return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2_t));
-  else return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
-// element h (0: low half, 1: high half) of a packed 16-bit pair as fp32
-template <bool F16>
-__device__ __forceinline__ float cunpack(uint32_t u, int h) {
-  if constexpr (F16) return (float)__builtin_bit_cast(_Float16, (uint16_t)(h ? (u >> 16) : (u & 0xffffu)));
-  else return __uint_as_float(h ? (u & 0xffff0000u) : (u << 16));
-}
+// (cmfma / cpack / cunpack, the 16-bit element type helpers of a conv, live in mfma.h)
 
 // Stream-K workspace (one per device and stream, conv_sk_workspace): a contributing segment's
 // fp32 partial tile [G][float4 slot][thread], a published flag per block (set with an agent-scope

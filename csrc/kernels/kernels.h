@@ -81,7 +81,18 @@ void launch_bn2_bwd_from_partials(int dtype, const void* dz, const void* x, cons
                                   float* dbeta2, void* dx, void* dx2, float* kbuf, hipStream_t s);
 void bn_set_skip_finalize(int on);  // measurement only (bench/ab_step.py): skip BN finalize launches
 void launch_bn_apply(int dtype, const void* x, const void* res, void* y, int64_t M, int64_t C,
-                     const float* coef_a, const float* coef_b, bool relu, hipStream_t s);
+                     const float* coef_a, const float* coef_b, bool relu, hipStream_t s, uint8_t* mask = nullptr);
+
+// tail_conv1_kernels.hip: a block tail's apply y = relu(x3*a + b + r) (coef2 == nullptr) or
+// relu(x3*a + b + r*a2 + b2), its 1-bit ReLU mask, and the 1x1 / stride-1 conv x1 = y w^T with the
+// BN partials psum/psq [Cout][conv_m_tiles(M)], in one kernel.  x3, r, y [M, Cin]; w [Cout][Cin];
+// x1 [M, Cout]; coef = [a | b], coef2 = [a2 | b2].  y, mask, x1, psum and psq are bit-equal to
+// launch_bn_apply / launch_bn_apply_aff followed by the unsplit launch_conv_fwd.
+// tail_conv1_refusal: nullptr when the kernel takes the shape, else why not (the launch throws it).
+const char* tail_conv1_refusal(int64_t M, int64_t Cin, int64_t Cout);
+void launch_tail_conv1_fwd(bool f16, const uint16_t* x3, const uint16_t* r, const float* coef, const float* coef2,
+                           const uint16_t* w, uint16_t* y, uint8_t* mask, uint16_t* x1, float* psum, float* psq,
+                           int64_t M, int Cin, int Cout, hipStream_t s);
 void launch_bn_bwd(int dtype, const void* dy, const void* dy2, const void* y, const void* x, int64_t M,
                    int64_t C, const float* gamma, const float* mean, const float* invstd, const float* coef,
                    float* dgamma, float* dbeta, void* dx, void* dz, float* workspace, bool relu, hipStream_t s);

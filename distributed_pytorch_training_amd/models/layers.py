@@ -32,11 +32,12 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
             return False
         return fused_bn.bn_act_supported(x, self.num_features)
 
-    def act(self, x: torch.Tensor, relu: bool, residual: Optional[torch.Tensor], pair: bool = False):
+    def act(self, x: torch.Tensor, relu: bool, residual: Optional[torch.Tensor], pair: bool = False,
+            consumer: Optional[nn.Module] = None):
         if self.training:
             return fused_bn.bn_act_train(x, residual, self.weight, self.bias, self.running_mean,
                                          self.running_var, self.num_batches_tracked, self.momentum,
-                                         self.eps, relu, pair)
+                                         self.eps, relu, pair, consumer)
         y = fused_bn.bn_act_eval(x, residual, self.weight, self.bias, self.running_mean,
                                  self.running_var, self.eps, relu)
         return (y, y) if pair else y
@@ -85,22 +86,24 @@ def downsample_branch(ds: nn.Module, x: torch.Tensor, tail_bn: nn.Module):
     return ds(x)
 
 
-def bn_act_block_out(bn: nn.Module, x: torch.Tensor, residual):
+def bn_act_block_out(bn: nn.Module, x: torch.Tensor, residual, consumer: Optional[nn.Module] = None):
     """Residual-block tail ``relu(bn(x) + residual)``.
 
     With a fused BN it returns ``(y_conv, y_identity)``: two aliases of the output whose
     gradients reach the fused backward separately (see ops/bn.py ``_BNActTrainPair``); the
     next block feeds the first to its conv path and the second to its identity path.
     Otherwise it returns the plain tensor.  ``residual`` may be a ``DeferredBN`` (downsample
-    branch): both BatchNorms then run as one fused op.
+    branch): both BatchNorms then run as one fused op.  ``consumer``: the conv module that reads the
+    conv-path alias next (the following block's ``conv1``, models/resnet.py); a fused tail may
+    leave its apply pass to that conv's forward (ops/bn.py ``TAIL_CONV1_FUSE``).
     """
     if isinstance(residual, DeferredBN):
         if (isinstance(bn, FusedBatchNorm2d) and bn.can_fuse(x) and bn.training
                 and residual.x.shape == x.shape and residual.x.dtype == x.dtype):
-            return fused_bn.bn2_add_relu_train(x, bn, residual.x, residual.bn)
+            return fused_bn.bn2_add_relu_train(x, bn, residual.x, residual.bn, consumer)
         residual = residual.materialize()
     if isinstance(bn, FusedBatchNorm2d) and bn.can_fuse(x):
-        return bn.act(x, True, residual, pair=True)
+        return bn.act(x, True, residual, pair=True, consumer=consumer)
     return bn_act(bn, x, True, residual)
 
 

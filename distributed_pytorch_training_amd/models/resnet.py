@@ -84,7 +84,20 @@ class Bottleneck(nn.Module):
         # so conv1's backward-data sees the whole identity-path gradient (ops/bn.py block tails)
         identity = xi if self.downsample is None else downsample_branch(self.downsample, xi, self.bn3)
         out = bn_act(self.bn2, self.conv2(out))
-        return bn_act_block_out(self.bn3, self.conv3(out), identity)
+        nxt = self.__dict__.get("dpt_tail_next")  # link_tail_consumers
+        return bn_act_block_out(self.bn3, self.conv3(out), identity, None if nxt is None else nxt.conv1)
+
+
+def link_tail_consumers(stages) -> None:
+    """Tell every Bottleneck which conv reads its tail's conv-path output: the next block's ``conv1``,
+    across a stage boundary too (the last block has none).  A fused tail may hand its apply pass to
+    that conv's forward (layers.bn_act_block_out).  The reference (to the next block: its ``conv1`` is
+    looked up at call time, after the engine has swapped conv classes) goes into the block's
+    ``__dict__``, not its submodules: state-dict keys and parameter counts are unchanged."""
+    blocks = [b for stage in stages for b in stage]
+    for blk, nxt in zip(blocks, blocks[1:]):
+        if isinstance(blk, Bottleneck) and isinstance(nxt, Bottleneck):
+            blk.__dict__["dpt_tail_next"] = nxt
 
 
 class ResNet(nn.Module):
@@ -102,6 +115,7 @@ class ResNet(nn.Module):
         self.layer4 = self._make_layer(block, 512, layers[3], stride=2)
         self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
         self.fc = nn.Linear(512 * block.expansion, num_classes)
+        link_tail_consumers([self.layer1, self.layer2, self.layer3, self.layer4])
 
         # torchvision init: Kaiming-normal(fan_out) convs, BN gamma=1 / beta=0,
         # Linear keeps PyTorch's default (kaiming-uniform a=sqrt(5)).

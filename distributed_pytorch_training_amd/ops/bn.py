@@ -24,10 +24,15 @@ import torch
 import os
 
 from . import native, native_available
-from .conv import COMPACT_RES, MASKED_NO_RES, take_bnb_partials
+from .conv import COMPACT_RES, MASKED_NO_RES, materialize_tail, take_bnb_partials
 
 # Block-tail BN+add+ReLU backward statistics in the consuming conv's dgrad epilogue (see _bwd)
 BNR_FUSE = os.environ.get("DPT_BNR_FUSE", "1") != "0"
+# A bottleneck tail whose conv-path output feeds a contracting 1x1 / stride-1 conv with one
+# output-channel tile (64 or 128 channels: ResNet-50's layer1 / layer2 conv1s) leaves its apply
+# pass to that conv's forward (csrc/kernels/tail_conv1_kernels.hip): one kernel writes y, the ReLU
+# mask and the conv output, and y is not read back from HBM.  0 = the two kernels.
+TAIL_CONV1_FUSE = os.environ.get("DPT_TAIL_CONV1_FUSE", "1") != "0"
 
 
 def _cl(t: torch.Tensor) -> torch.Tensor:
@@ -78,13 +83,23 @@ class _BNActTrainPair(torch.autograd.Function):
 def _fwd(ctx, x, residual, weight, bias, running_mean, running_var, num_batches, momentum, eps, relu,
          pair=False, partials=None, links=(None, None)):
     ps, pq = partials if partials is not None else (None, None)
-    own_slot, res_slot = links
+    own_slot, res_slot = links[0], links[1]
+    defer = links[2] if len(links) > 2 else None
     # block tail whose output feeds a native conv: the 1-bit ReLU mask that conv's dgrad epilogue
     # reads instead of y (1/16 of y's bytes; ops/conv.py BNR)
     mask = _relu_mask(x) if (own_slot is not None and relu and residual is not None) else None
-    y, mean, invstd, coef = native().bn_fwd_train(x, residual, weight, bias, running_mean, running_var,
-                                                  num_batches, float(momentum), float(eps), bool(relu), ps, pq,
-                                                  mask_out=mask)
+    if defer is not None:
+        # TAIL_CONV1_FUSE: statistics, running statistics and coefficients now; y and the mask are
+        # filled by the consuming conv's forward (run_tail_consumer, right after this op)
+        _, mean, invstd, coef = native().bn_fwd_train(x, residual, weight, bias, running_mean, running_var,
+                                                      num_batches, float(momentum), float(eps), bool(relu), ps, pq,
+                                                      False)
+        y = torch.empty_like(x)
+        defer.update(x3=x, r=residual, coef=coef, coef2=None, y=y, mask=mask)
+    else:
+        y, mean, invstd, coef = native().bn_fwd_train(x, residual, weight, bias, running_mean, running_var,
+                                                      num_batches, float(momentum), float(eps), bool(relu), ps, pq,
+                                                      mask_out=mask)
     ctx.relu = bool(relu)
     ctx.has_res = residual is not None
     mask_from_x = ctx.relu and not ctx.has_res and not pair   # pair outputs always write dz
@@ -167,7 +182,7 @@ class _BN2AddReLUPair(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, x2, w, b, rm, rv, nb, w2, b2, rm2, rv2, nb2, momentum, eps, momentum2, eps2,
-                partials, partials2, own_slot):
+                partials, partials2, own_slot, defer):
         C = native()
         ps, pq = partials if partials is not None else (None, None)
         ps2, pq2 = partials2 if partials2 is not None else (None, None)
@@ -176,7 +191,11 @@ class _BN2AddReLUPair(torch.autograd.Function):
         _, mean2, invstd2, coef2 = C.bn_fwd_train(x2, None, w2, b2, rm2, rv2, nb2, float(momentum2), float(eps2),
                                                   False, ps2, pq2, False)
         mask = _relu_mask(x) if own_slot is not None else None
-        y = C.bn_apply_aff(x, x2, coef, coef2, mask_out=mask)
+        if defer is not None:  # TAIL_CONV1_FUSE: the consuming conv's forward fills y and the mask
+            y = torch.empty_like(x)
+            defer.update(x3=x, r=x2, coef=coef, coef2=coef2, y=y, mask=mask)
+        else:
+            y = C.bn_apply_aff(x, x2, coef, coef2, mask_out=mask)
         ctx.save_for_backward(x, x2, y, w, w2, mean, invstd, mean2, invstd2)
         ctx.set_materialize_grads(False)
         if own_slot is not None:
@@ -190,7 +209,7 @@ class _BN2AddReLUPair(torch.autograd.Function):
         if dy is None:
             dy, dy2 = dy2, None
         if dy is None:
-            return (None,) * 19
+            return (None,) * 20
         want = [ctx.needs_input_grad[i] for i in (2, 3, 7, 8)]
         want_params = any(want)
         C = native()
@@ -210,21 +229,56 @@ class _BN2AddReLUPair(torch.autograd.Function):
                                         bool(want_params), None)
         g = [dg, db, dg2, db2]
         g = [t if (want_params and want[i]) else None for i, t in enumerate(g)]
-        return (dx, dx2, g[0], g[1], None, None, None, g[2], g[3]) + (None,) * 10
+        return (dx, dx2, g[0], g[1], None, None, None, g[2], g[3]) + (None,) * 11
 
 
-def bn2_add_relu_train(x, bn, x2, bn2):
+def _tail_defer(x, own_slot, consumer):
+    """A fresh hand-over dict when the tail on ``x`` may leave its apply pass to ``consumer`` (the
+    conv module that reads the tail's conv-path output, models/resnet.py), else None."""
+    if not (TAIL_CONV1_FUSE and consumer is not None and own_slot is not None and torch.is_grad_enabled()):
+        return None
+    w = getattr(consumer, "weight", None)
+    if w is None or w.dim() != 4 or tuple(w.shape[1:]) != (x.shape[1], 1, 1):
+        return None
+    if getattr(consumer, "dpt_native_conv", True) is False:
+        return None
+    m = x.shape[0] * x.shape[2] * x.shape[3]
+    return {} if native().conv1x1_tail_refusal(m, x.shape[1], w.shape[0]) is None else None
+
+
+def run_tail_consumer(out, defer, consumer) -> None:
+    """Run ``consumer`` on the conv-path alias ``out[0]`` of a tail whose apply pass was deferred:
+    the conv's forward (ops/conv.py) fills the tail's output and mask while it stages them.  The
+    result waits on the alias for the next block's call of the same conv.  Whatever ``consumer``
+    turns out to do, the tail's output is filled when this returns."""
+    yc = out[0]
+    yc._dpt_tail_pending = defer
+    try:
+        consumer(yc)
+    finally:
+        yc.__dict__.pop("_dpt_tail_pending", None)
+        if not defer.get("done"):  # the call never reached the native conv: its result is void
+            materialize_tail(defer)
+            defer.pop("conv", None)
+    if "conv" in defer:
+        yc._dpt_conv1_out = defer["conv"]
+
+
+def bn2_add_relu_train(x, bn, x2, bn2, consumer=None):
     """Block tail ``relu(bn(x) + bn2(x2))`` in training mode (both ``FusedBatchNorm2d``), pair
     outputs (conv path, identity path) - see _BN2AddReLUPair."""
     x2 = _cl(x2.to(x.dtype))
     partials = x.__dict__.pop("_dpt_bn_partials", None)
     partials2 = x2.__dict__.pop("_dpt_bn_partials", None)
     own_slot = {} if (BNR_FUSE and x.dtype in (torch.bfloat16, torch.float16)) else None
+    defer = _tail_defer(x, own_slot, consumer)
     out = _BN2AddReLUPair.apply(x, x2, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                 bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var, bn2.num_batches_tracked,
-                                bn.momentum, bn.eps, bn2.momentum, bn2.eps, partials, partials2, own_slot)
+                                bn.momentum, bn.eps, bn2.momentum, bn2.eps, partials, partials2, own_slot, defer)
     if own_slot is not None:
         out[1]._dpt_res_slot = own_slot
+    if defer is not None:
+        run_tail_consumer(out, defer, consumer)
     return out
 
 
@@ -236,7 +290,7 @@ def bn_act_supported(x: torch.Tensor, num_features: int) -> bool:
 
 
 def bn_act_train(x: torch.Tensor, residual: Optional[torch.Tensor], weight, bias, running_mean, running_var,
-                 num_batches, momentum: float, eps: float, relu: bool, pair: bool = False):
+                 num_batches, momentum: float, eps: float, relu: bool, pair: bool = False, consumer=None):
     res_slot = None
     if residual is not None:
         if residual.dtype == x.dtype and residual.is_contiguous(memory_format=torch.channels_last):
@@ -250,10 +304,13 @@ def bn_act_train(x: torch.Tensor, residual: Optional[torch.Tensor], weight, bias
     own_slot = {} if (pair and relu and residual is not None and BNR_FUSE
                       and x.dtype in (torch.bfloat16, torch.float16)) else None
     fn = _BNActTrainPair if pair else _BNActTrain
+    defer = _tail_defer(x, own_slot, consumer)
     out = fn.apply(x, residual, weight, bias, running_mean, running_var, num_batches, momentum, eps, relu,
-                   partials, (own_slot, res_slot))
+                   partials, (own_slot, res_slot, defer))
     if own_slot is not None:
         out[1]._dpt_res_slot = own_slot
+    if defer is not None:
+        run_tail_consumer(out, defer, consumer)
     return out
 
 

@@ -281,12 +281,48 @@ class _Conv(torch.autograd.Function):
         return _backward(ctx, dy) + (None,) * 6
 
 
+def materialize_tail(pending) -> None:
+    """Fill a block tail's deferred output ``y`` (and its ReLU mask) with the apply kernel the tail
+    itself would have launched (ops/bn.py TAIL_CONV1_FUSE), once."""
+    if pending.get("done"):
+        return
+    x3, r, coef, coef2 = pending["x3"], pending["r"], pending["coef"], pending["coef2"]
+    c = x3.shape[1]
+    if coef2 is None:
+        native().bn_apply(x3, r, coef[:c], coef[c:], True, mask_out=pending["mask"], y_out=pending["y"])
+    else:
+        native().bn_apply_aff(x3, r, coef, coef2, mask_out=pending["mask"], y_out=pending["y"])
+    pending["done"] = True
+
+
+def _tail_fwd(x, w, stride, pad, out_hw, pending):
+    """The forward of a conv whose input ``x`` is a block tail's still unfilled output: one kernel
+    writes ``x``, its mask and the conv output.  A conv the kernel refuses first materialises ``x``
+    with the tail's own apply pass; None then, and the caller runs the plain forward."""
+    if pending["y"].data_ptr() != x.data_ptr() or tuple(out_hw) != (0, 0):
+        materialize_tail(pending)
+        return None
+    try:
+        out = native().conv1x1_tail_fwd(pending["x3"], pending["r"], pending["coef"], pending["coef2"], w, x,
+                                        pending["mask"], stride, pad)
+    except RuntimeError:
+        materialize_tail(pending)
+        return None
+    pending["done"] = True
+    return out
+
+
 class _ConvStats(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, stride: int, pad: int, out_hw, bn_src, res_slot, compact_dres):
+    def forward(ctx, x, w, stride: int, pad: int, out_hw, bn_src, res_slot, compact_dres, pending):
         e0 = _mark()
-        y, ps, pq = native().conv_fwd(x, w, stride, pad, True, *out_hw)
-        _note("fwd", x, w, stride, pad, "stats", e0, out_hw)
+        fused = _tail_fwd(x, w, stride, pad, out_hw, pending) if pending is not None else None
+        if fused is not None:
+            y, ps, pq = fused
+            _note("fwd", x, w, stride, pad, "tail-apply+stats", e0, out_hw)
+        else:
+            y, ps, pq = native().conv_fwd(x, w, stride, pad, True, *out_hw)
+            _note("fwd", x, w, stride, pad, "stats", e0, out_hw)
         ctx.save_for_backward(x, w)
         ctx.stride, ctx.pad, ctx.bn_src, ctx.res_slot = stride, pad, bn_src, res_slot
         ctx.compact_dres = compact_dres
@@ -296,7 +332,7 @@ class _ConvStats(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, _dps, _dpq):
-        return _backward(ctx, dy) + (None,) * 6
+        return _backward(ctx, dy) + (None,) * 7
 
 
 def conv2d(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, bn_stats: bool = False,
@@ -305,6 +341,17 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, bn_stats: bo
     BatchNorm partial sums as ``y._dpt_bn_partials`` (consumed by ops/bn.py).  ``out_hw``:
     explicit output size (asymmetric padding: top/left ``pad``, bottom/right what fits)."""
     w = _cl(w)
+    # the tail that produced x already ran this very conv on it, fused with its apply pass
+    # (ops/bn.py TAIL_CONV1_FUSE): hand that result over
+    done = x.__dict__.pop("_dpt_conv1_out", None)
+    if done is not None and done[0] is w and done[1:4] == (int(stride), int(pad), bool(bn_stats)) \
+            and tuple(out_hw) == (0, 0):
+        return done[4]
+    # x is a block tail's output that is not filled yet: this conv's forward fills it
+    pending = x.__dict__.pop("_dpt_tail_pending", None)
+    if pending is not None and not bn_stats:
+        materialize_tail(pending)
+        pending = None
     if _FLIP["on"] and int(stride) == 1 and x.requires_grad:
         _FLIP["pending"].setdefault((w.data_ptr(), tuple(w.shape)), w)
     # (BN input, mean, coef) of the fused BN+ReLU that produced x, if any (ops/bn.py)
@@ -322,8 +369,11 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, bn_stats: bo
                         and tuple(out_hw) == (0, 0) and res_slot is not None and res_slot.get("fold_s2"))
     if not bn_stats:
         return _Conv.apply(x, w, int(stride), int(pad), tuple(out_hw), bn_src, res_slot, compact_dres)
-    y, ps, pq = _ConvStats.apply(x, w, int(stride), int(pad), tuple(out_hw), bn_src, res_slot, compact_dres)
+    y, ps, pq = _ConvStats.apply(x, w, int(stride), int(pad), tuple(out_hw), bn_src, res_slot, compact_dres,
+                                 pending)
     y._dpt_bn_partials = (ps, pq)
+    if pending is not None:  # fused or not, y is the result of this conv on the filled x
+        pending["conv"] = (w, int(stride), int(pad), True, y)
     return y
 
 
