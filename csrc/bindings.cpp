@@ -121,6 +121,127 @@ void optim_tail(c10::optional<Tensor> scale, c10::optional<Tensor> growth_tracke
                          cur_stream(found_inf));
 }
 
+// ---- LARS / LAMB (trust_kernels.hip) --------------------------------------------------------------
+int64_t trust_chunk() { return dpt::kTrustChunk; }
+
+// Validate a host-built chunk table against the arena it indexes, then copy it to the device of
+// `like`.  Every bound the kernels rely on is checked here, once, before any launch sees the table:
+// chunks [nchunks, 4] = (start, length, segment, 0), seg_first / seg_count / seg_flags [nseg].
+std::vector<Tensor> trust_segments(Tensor chunks, Tensor seg_first, Tensor seg_count, Tensor seg_flags,
+                                   int64_t arena_numel, Tensor like) {
+  auto host_i32 = [](const Tensor& t, const char* name) {
+    TORCH_CHECK(!t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous(), name,
+                " must be a contiguous int32 CPU tensor");
+  };
+  host_i32(chunks, "chunks");
+  host_i32(seg_first, "seg_first");
+  host_i32(seg_count, "seg_count");
+  host_i32(seg_flags, "seg_flags");
+  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 4, "chunks must be [nchunks, 4]");
+  const int64_t nchunks = chunks.size(0), nseg = seg_first.numel();
+  TORCH_CHECK(seg_count.numel() == nseg && seg_flags.numel() == nseg, "segment arrays differ in length");
+  TORCH_CHECK(arena_numel >= 0 && arena_numel < (int64_t(1) << 31) && arena_numel % 4 == 0,
+              "arena size must be a multiple of 4 below 2^31 elements");
+  const int* ch = chunks.data_ptr<int>();
+  const int* sf = seg_first.data_ptr<int>();
+  const int* sc = seg_count.data_ptr<int>();
+  const int* fl = seg_flags.data_ptr<int>();
+  int64_t next_chunk = 0, prev_end = 0;
+  for (int64_t sgi = 0; sgi < nseg; ++sgi) {
+    TORCH_CHECK(sf[sgi] == next_chunk && sc[sgi] >= 1, "segment ", sgi, ": chunks must be contiguous and in order");
+    TORCH_CHECK(next_chunk + sc[sgi] <= nchunks, "segment ", sgi, ": chunk range exceeds the table");
+    TORCH_CHECK((fl[sgi] & ~3) == 0, "segment ", sgi, ": unknown flag bits");
+    for (int64_t k = 0; k < sc[sgi]; ++k) {
+      const int* c = ch + 4 * (next_chunk + k);
+      const int64_t start = c[0], len = c[1], end4 = start + (len + 3) / 4 * 4;
+      TORCH_CHECK(c[2] == sgi, "chunk ", next_chunk + k, " names the wrong segment");
+      TORCH_CHECK(start >= prev_end && start % 4 == 0, "chunk ", next_chunk + k, " overlaps or is misaligned");
+      TORCH_CHECK(len >= 1 && len <= dpt::kTrustChunk && (k + 1 == sc[sgi] || len == dpt::kTrustChunk),
+                  "chunk ", next_chunk + k, ": only a segment's last chunk may be short");
+      TORCH_CHECK(k == 0 || start == prev_end, "chunk ", next_chunk + k, " does not follow its predecessor");
+      TORCH_CHECK(end4 <= arena_numel, "chunk ", next_chunk + k, " reaches past the arena");
+      prev_end = end4;
+    }
+    next_chunk += sc[sgi];
+  }
+  TORCH_CHECK(next_chunk == nchunks, "chunks that belong to no segment");
+  TORCH_CHECK(like.is_cuda(), "trust_segments uploads to a GPU: `like` must be a GPU tensor");
+  auto dev = like.device();
+  return {chunks.to(dev), seg_first.to(dev), seg_count.to(dev), seg_flags.to(dev)};
+}
+
+dpt::TrustTable trust_table(const Tensor& p, const Tensor& chunks, const Tensor& seg_first,
+                            const Tensor& seg_count, const Tensor& seg_flags, const Tensor& partial,
+                            const Tensor& ratio, int64_t table_numel) {
+  auto dev_i32 = [&](const Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == p.device() && t.scalar_type() == at::kInt && t.is_contiguous(),
+                name, " must be a contiguous int32 tensor on the arena's GPU");
+  };
+  dev_i32(chunks, "chunks");
+  dev_i32(seg_first, "seg_first");
+  dev_i32(seg_count, "seg_count");
+  dev_i32(seg_flags, "seg_flags");
+  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 4, "chunks must be [nchunks, 4]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(chunks.data_ptr()) % 16 == 0, "chunks must be 16-byte aligned");
+  const int64_t nchunks = chunks.size(0), nseg = seg_first.numel();
+  TORCH_CHECK(seg_count.numel() == nseg && seg_flags.numel() == nseg, "segment arrays differ in length");
+  TORCH_CHECK(nchunks < (int64_t(1) << 31), "too many chunks");
+  check_flat_f32(partial, "partial", 2);
+  check_flat_f32(ratio, "ratio", 1);
+  TORCH_CHECK(partial.device() == p.device() && ratio.device() == p.device(), "partial/ratio on another device");
+  TORCH_CHECK(partial.numel() >= 2 * nchunks, "partial must hold 2 floats per chunk");
+  TORCH_CHECK(ratio.numel() >= nseg, "ratio must hold one float per segment");
+  TORCH_CHECK(table_numel == p.numel(), "the segment table was validated for an arena of ", table_numel,
+              " elements, this one has ", p.numel());
+  dpt::TrustTable tb;
+  tb.chunks = chunks.data_ptr<int>();
+  tb.seg_first = seg_first.data_ptr<int>();
+  tb.seg_count = seg_count.data_ptr<int>();
+  tb.seg_flags = seg_flags.data_ptr<int>();
+  tb.nchunks = (int)nchunks;
+  tb.nseg = (int)nseg;
+  tb.partial = partial.data_ptr<float>();
+  tb.ratio = ratio.data_ptr<float>();
+  return tb;
+}
+
+void lars_step(Tensor p, Tensor g, Tensor buf, Tensor chunks, Tensor seg_first, Tensor seg_count,
+               Tensor seg_flags, Tensor partial, Tensor ratio, int64_t table_numel, double lr,
+               double momentum, double wd, double eta, bool nesterov, c10::optional<Tensor> scale,
+               double host_factor, c10::optional<Tensor> found_inf, c10::optional<Tensor> step,
+               bool zero_grad, c10::optional<Tensor> shadow) {
+  check_flat_f32(p, "param");
+  check_flat_f32(g, "grad");
+  check_flat_f32(buf, "momentum_buffer");
+  TORCH_CHECK(g.numel() == p.numel() && buf.numel() == p.numel(), "lars arena size mismatch");
+  auto tb = trust_table(p, chunks, seg_first, seg_count, seg_flags, partial, ratio, table_numel);
+  auto [sp, sk] = shadow_arg(shadow, p.numel());
+  c10::hip::HIPGuard guard(p.device().index());
+  dpt::launch_lars(p.data_ptr<float>(), g.data_ptr<float>(), buf.data_ptr<float>(), tb, (float)lr,
+                   (float)momentum, (float)wd, (float)eta, nesterov, opt_f32(scale, "scale"),
+                   (float)host_factor, opt_f32(found_inf, "found_inf"), opt_f32(step, "step"), zero_grad,
+                   sp, sk, cur_stream(p));
+}
+
+void lamb_step(Tensor p, Tensor g, Tensor m, Tensor v, Tensor chunks, Tensor seg_first, Tensor seg_count,
+               Tensor seg_flags, Tensor partial, Tensor ratio, int64_t table_numel, double lr,
+               double beta1, double beta2, double eps, double wd, c10::optional<Tensor> scale,
+               double host_factor, c10::optional<Tensor> found_inf, c10::optional<Tensor> step,
+               bool zero_grad, c10::optional<Tensor> shadow) {
+  check_flat_f32(p, "param");
+  check_flat_f32(g, "grad");
+  check_flat_f32(m, "exp_avg");
+  check_flat_f32(v, "exp_avg_sq");
+  TORCH_CHECK(g.numel() == p.numel() && m.numel() == p.numel() && v.numel() == p.numel(),
+              "lamb arena size mismatch");
+  auto tb = trust_table(p, chunks, seg_first, seg_count, seg_flags, partial, ratio, table_numel);
+  auto [sp, sk] = shadow_arg(shadow, p.numel());
+  c10::hip::HIPGuard guard(p.device().index());
+  dpt::launch_lamb(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), tb,
+                   lr, beta1, beta2, eps, wd, opt_f32(scale, "scale"), (float)host_factor,
+                   opt_f32(found_inf, "found_inf"), opt_f32(step, "step"), zero_grad, sp, sk, cur_stream(p));
+}
+
 void pack_bf16(Tensor src, Tensor dst) {
   check_flat_f32(src, "src", 8);
   TORCH_CHECK(dst.is_cuda() && dst.scalar_type() == at::kBFloat16 && dst.is_contiguous() &&
@@ -1339,6 +1460,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"), py::arg("adamw"),
         py::arg("scale"), py::arg("host_factor"), py::arg("found_inf"), py::arg("step"), py::arg("zero_grad"),
         py::arg("shadow") = py::none());
+  m.def("trust_chunk", &trust_chunk);
+  m.def("trust_segments", &trust_segments, py::arg("chunks"), py::arg("seg_first"), py::arg("seg_count"),
+        py::arg("seg_flags"), py::arg("arena_numel"), py::arg("like"));
+  m.def("lars_step", &lars_step, py::arg("param"), py::arg("grad"), py::arg("momentum_buffer"),
+        py::arg("chunks"), py::arg("seg_first"), py::arg("seg_count"), py::arg("seg_flags"), py::arg("partial"),
+        py::arg("ratio"), py::arg("table_numel"), py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"),
+        py::arg("eta"), py::arg("nesterov"), py::arg("scale"), py::arg("host_factor"), py::arg("found_inf"),
+        py::arg("step"), py::arg("zero_grad"), py::arg("shadow") = py::none());
+  m.def("lamb_step", &lamb_step, py::arg("param"), py::arg("grad"), py::arg("exp_avg"), py::arg("exp_avg_sq"),
+        py::arg("chunks"), py::arg("seg_first"), py::arg("seg_count"), py::arg("seg_flags"), py::arg("partial"),
+        py::arg("ratio"), py::arg("table_numel"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("weight_decay"), py::arg("scale"), py::arg("host_factor"), py::arg("found_inf"),
+        py::arg("step"), py::arg("zero_grad"), py::arg("shadow") = py::none());
   m.def("optim_tail", &optim_tail, py::arg("scale"), py::arg("growth_tracker"), py::arg("found_inf"),
         py::arg("step"), py::arg("growth_factor"), py::arg("backoff_factor"), py::arg("growth_interval"));
   m.def("pack_bf16", &pack_bf16);

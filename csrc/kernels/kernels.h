@@ -29,6 +29,27 @@ void launch_optim_tail(float* scale, int* growth_tracker, float* found_inf, floa
                        float growth_factor, float backoff_factor, int growth_interval,
                        hipStream_t s);
 
+// trust_kernels.hip: LARS / LAMB with per-parameter trust ratios.  The table (device pointers,
+// built and bounds-checked by the caller) cuts every parameter into chunks of kTrustChunk
+// elements that never cross a parameter boundary; chunks holds int4 (start, length, segment, 0).
+constexpr int kTrustChunk = 4096;
+struct TrustTable {
+  const int* chunks;
+  const int* seg_first;
+  const int* seg_count;
+  const int* seg_flags;   // bit 0: adapt (trust ratio), bit 1: decay (weight decay)
+  int nchunks, nseg;
+  float* partial;         // [nchunks][2] per-chunk sums of squares
+  float* ratio;           // [nseg]
+};
+void launch_lars(float* p, float* g, float* buf, const TrustTable& tb, float lr, float momentum, float wd,
+                 float eta, bool nesterov, const float* scale, float host_factor, const float* found_inf,
+                 const float* step, bool zero_grad, uint16_t* shadow, int shadow_kind, hipStream_t s);
+void launch_lamb(float* p, float* g, float* m, float* v, const TrustTable& tb, double lr, double beta1,
+                 double beta2, double eps, double wd, const float* scale, float host_factor,
+                 const float* found_inf, const float* step, bool zero_grad, uint16_t* shadow,
+                 int shadow_kind, hipStream_t s);
+
 // comm_kernels.hip
 void launch_pack_bf16(const float* src, uint16_t* dst, int64_t n, hipStream_t s);
 void launch_unpack_bf16(const uint16_t* src, float* dst, int64_t n, const float* scale,

@@ -64,11 +64,17 @@ def build_parser() -> argparse.ArgumentParser:
                    help="pixel noise std of --synthetic-task prototypes (prototypes have unit std)")
     g.add_argument("--amp-dtype", default="fp16", choices=["fp16", "bf16"],
                    help="autocast dtype when --amp is set (reference: fp16)")
-    g.add_argument("--optimizer", default="sgd", choices=["sgd", "adam", "adamw"],
-                   help="optimizer (reference: sgd)")
-    g.add_argument("--nesterov", action="store_true", help="Nesterov momentum (SGD)")
-    g.add_argument("--betas", default="0.9,0.999", type=str, help="Adam betas")
-    g.add_argument("--eps", default=1e-8, type=float, help="Adam epsilon")
+    g.add_argument("--optimizer", default="sgd", choices=["sgd", "adam", "adamw", "lars", "lamb"],
+                   help="optimizer (reference: sgd); lars / lamb scale each parameter's update by a "
+                        "trust ratio of its norms (large global batches)")
+    g.add_argument("--nesterov", action="store_true", help="Nesterov momentum (SGD, LARS)")
+    g.add_argument("--betas", default="0.9,0.999", type=str, help="Adam / LAMB betas")
+    g.add_argument("--eps", default=1e-8, type=float, help="Adam / LAMB epsilon")
+    g.add_argument("--trust-coefficient", default=0.001, type=float,
+                   help="LARS eta: ratio = eta |w| / (|g| + wd |w|) (ignored by the other optimizers)")
+    g.add_argument("--adapt-1d", action="store_true",
+                   help="lars / lamb: also give 1-D parameters (biases, BatchNorm / LayerNorm weights) a "
+                        "trust ratio and weight decay; off: they get neither")
     g.add_argument("--impl", default="native", choices=["native", "torch"],
                    help="native: MI355X engine (HIP kernels, RCCL reducer); torch: stock DDP/foreach SGD/GradScaler")
     g.add_argument("--backend", default="auto", choices=["auto", "rccl", "nccl", "gloo"],

@@ -178,6 +178,16 @@ class Trainer:
             self.optimizer = torch.optim.SGD(params, lr=args.lr, momentum=args.momentum,
                                              weight_decay=args.weight_decay,
                                              nesterov=getattr(args, "nesterov", False))
+        elif args.optimizer == "lars":
+            from ..optim.stock import LARS
+            self.optimizer = LARS(params, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
+                                  nesterov=getattr(args, "nesterov", False),
+                                  trust_coefficient=getattr(args, "trust_coefficient", 0.001),
+                                  adapt_1d=getattr(args, "adapt_1d", False))
+        elif args.optimizer == "lamb":
+            from ..optim.stock import LAMB
+            self.optimizer = LAMB(params, lr=args.lr, betas=args.betas, eps=args.eps,
+                                  weight_decay=args.weight_decay, adapt_1d=getattr(args, "adapt_1d", False))
         elif args.optimizer == "adam":
             self.optimizer = torch.optim.Adam(params, lr=args.lr, betas=args.betas, eps=args.eps,
                                               weight_decay=args.weight_decay)

@@ -11,7 +11,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import reference
+from . import reference, trust
 
 def _load():
     """The in-tree extension built by csrc/build.py, or the file named by ``DPT_NATIVE_LIB``
@@ -99,6 +99,51 @@ def optim_tail(scale, growth_tracker, found_inf, step, growth_factor=2.0, backof
                              backoff_factor, growth_interval)
 
 
+def trust_chunk() -> int:
+    """Elements per chunk of the LARS / LAMB segment table (a compile-time constant of the kernels)."""
+    if _C is not None:
+        n = int(_C.trust_chunk())
+        if n != trust.TRUST_CHUNK:
+            raise RuntimeError(f"ops/trust.py TRUST_CHUNK {trust.TRUST_CHUNK} != kTrustChunk {n}")
+    return trust.TRUST_CHUNK
+
+
+def trust_segments(offsets, numels, flags, arena_numel: int, device) -> "trust.TrustTable":
+    """Build (and for a GPU arena validate and upload) the segment table: ops/trust.py."""
+    gpu = torch.device(device).type == "cuda"
+    if gpu:
+        trust_chunk()
+    return trust.build_table(offsets, numels, flags, arena_numel, device, native() if gpu else None)
+
+
+def lars_step(param, grad, momentum_buffer, table, ratio, *, lr, momentum, weight_decay, eta, nesterov,
+              scale=None, host_factor=1.0, found_inf=None, step=None, zero_grad=True, shadow=None) -> None:
+    if _gpu(param):
+        native().lars_step(param, grad, momentum_buffer, *table.device_tensors, table.partial, ratio,
+                           table.numel, float(lr), float(momentum), float(weight_decay), float(eta),
+                           bool(nesterov), scale, float(host_factor), found_inf, step, bool(zero_grad),
+                           shadow)
+    else:
+        reference.lars_step(param, grad, momentum_buffer, table, ratio, lr, momentum, weight_decay, eta,
+                            nesterov, scale, host_factor, found_inf, step, zero_grad)
+        if shadow is not None:
+            shadow.copy_(param)
+
+
+def lamb_step(param, grad, exp_avg, exp_avg_sq, table, ratio, *, lr, beta1, beta2, eps, weight_decay,
+              scale=None, host_factor=1.0, found_inf=None, step=None, zero_grad=True, shadow=None) -> None:
+    if _gpu(param):
+        native().lamb_step(param, grad, exp_avg, exp_avg_sq, *table.device_tensors, table.partial, ratio,
+                           table.numel, float(lr), float(beta1), float(beta2), float(eps),
+                           float(weight_decay), scale, float(host_factor), found_inf, step,
+                           bool(zero_grad), shadow)
+    else:
+        reference.lamb_step(param, grad, exp_avg, exp_avg_sq, table, ratio, lr, beta1, beta2, eps,
+                            weight_decay, scale, host_factor, found_inf, step, zero_grad)
+        if shadow is not None:
+            shadow.copy_(param)
+
+
 def accumulate_metrics(logits, targets, loss, acc) -> None:
     if _gpu(logits):
         native().accumulate_metrics(logits.detach(), targets, loss, acc)
@@ -130,4 +175,4 @@ def unpack_bf16(src, dst, scale=None, host_factor=1.0, found_inf=None) -> None:
 
 
 __all__ = ["native_available", "native", "grad_check", "sgd_step", "adam_step", "optim_tail",
-           "accumulate_metrics", "augment", "pack_bf16", "unpack_bf16", "reference"]
+           "trust_chunk", "trust_segments", "lars_step", "lamb_step", "trust", "accumulate_metrics", "augment", "pack_bf16", "unpack_bf16", "reference"]

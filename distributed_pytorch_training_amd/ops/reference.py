@@ -74,6 +74,67 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_de
         grad.zero_()
 
 
+def _trust_ratio(flags: int, wn: torch.Tensor, xn: torch.Tensor, lars_eta, wd_i: float) -> torch.Tensor:
+    """LARS (``lars_eta`` given): eta wn / (xn + wd_i wn); LAMB: wn / xn; 1 where not adapted or a
+    norm is zero."""
+    one = torch.ones((), dtype=torch.float32, device=wn.device)
+    if not (flags & 1) or not (float(wn) > 0.0 and float(xn) > 0.0):
+        return one
+    return lars_eta * wn / (xn + wd_i * wn) if lars_eta is not None else wn / xn
+
+
+@torch.no_grad()
+def lars_step(param, grad, momentum_buffer, table, ratio, lr, momentum, weight_decay, eta, nesterov,
+              scale, host_factor, found_inf, step, zero_grad) -> None:
+    """LARS over the segments of ``table`` (ops/trust.py), fp32, one segment after the other:
+    ratio = eta ||p|| / (||g|| + wd_i ||p||), d = ratio (g + wd_i p), buf = d | mu buf + d,
+    p -= lr (nesterov ? d + mu buf : buf)."""
+    skip = found_inf is not None and float(found_inf.reshape(-1)[0]) != 0.0
+    if not skip:
+        f = _factor(scale, host_factor)
+        first = step is None or float(step.reshape(-1)[0]) == 0.0
+        for i, (off, n, fl) in enumerate(zip(table.offsets, table.numels, table.flags)):
+            p, buf = param[off:off + n], momentum_buffer[off:off + n]
+            g = grad[off:off + n] * f
+            wd_i = weight_decay if fl & 2 else 0.0
+            r = _trust_ratio(fl, p.norm(), g.norm(), eta, wd_i)
+            ratio[i] = r
+            d = (g.add(p, alpha=wd_i) if wd_i != 0 else g) * r
+            if first:
+                buf.copy_(d)
+            else:
+                buf.mul_(momentum).add_(d)
+            p.add_(d.add(buf, alpha=momentum) if nesterov else buf, alpha=-lr)
+    if zero_grad:
+        grad.zero_()
+
+
+@torch.no_grad()
+def lamb_step(param, grad, exp_avg, exp_avg_sq, table, ratio, lr, beta1, beta2, eps, weight_decay,
+              scale, host_factor, found_inf, step, zero_grad) -> None:
+    """LAMB over the segments of ``table``: Adam moments, u = (m / bc1) / (sqrt(v / bc2) + eps) + wd_i p,
+    ratio = ||p|| / ||u||, p -= lr ratio u."""
+    skip = found_inf is not None and float(found_inf.reshape(-1)[0]) != 0.0
+    if not skip:
+        f = _factor(scale, host_factor)
+        t = (float(step.reshape(-1)[0]) if step is not None else 0.0) + 1.0
+        bc1, bc2 = 1 - beta1 ** t, 1 - beta2 ** t
+        for i, (off, n, fl) in enumerate(zip(table.offsets, table.numels, table.flags)):
+            p, m, v = param[off:off + n], exp_avg[off:off + n], exp_avg_sq[off:off + n]
+            g = grad[off:off + n] * f
+            wd_i = weight_decay if fl & 2 else 0.0
+            m.lerp_(g, 1 - beta1)
+            v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+            u = (m / bc1) / ((v / bc2).sqrt_().add_(eps))
+            if wd_i != 0:
+                u.add_(p, alpha=wd_i)
+            r = _trust_ratio(fl, p.norm(), u.norm(), None, wd_i)
+            ratio[i] = r
+            p.sub_(u * (lr * r))
+    if zero_grad:
+        grad.zero_()
+
+
 @torch.no_grad()
 def optim_tail(scale, growth_tracker, found_inf, step, growth_factor, backoff_factor,
                growth_interval) -> None:

@@ -211,7 +211,187 @@ class FusedAdam(_FlatOptimizer):
             self._step.fill_(float(torch.as_tensor(get(0)["step"]).item()))
 
 
+class _TrustOptimizer(_FlatOptimizer):
+    """Shared by FusedLARS / FusedLAMB: the segment table (ops/trust.py), keyed on the arena's layout.
+
+    ``NativeDDP.maybe_rebuild_buckets`` re-lays the arena once, after the first backward and before
+    that step's ``optimizer.step``; the table is rebuilt by the first ``step`` that sees the new
+    layout.  Building uploads host data, which a captured stream cannot do: the eager warm-up steps
+    of engine/graph.py come after the relayout, so a capture always finds the table built, and
+    ``_ensure_table`` raises if it does not.
+    """
+
+    def __init__(self, arena, params_in_order, defaults, adapt_1d: bool) -> None:
+        super().__init__(arena, params_in_order, defaults)
+        self.adapt_1d = bool(adapt_1d)
+        self._table = None
+        self._table_layout = None      # (offsets list, param_flat) the table was built for
+
+    def _layout_is_current(self) -> bool:
+        lay = self._table_layout
+        return lay is not None and lay[0] is self.arena.offsets and lay[1] is self.arena.param_flat
+
+    def _capturing(self) -> bool:
+        return self.arena.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+
+    def _ensure_table(self):
+        if self._table is None or not self._layout_is_current():
+            if self._capturing():
+                raise RuntimeError("the trust-ratio segment table must be built by an eager step before "
+                                   "the step is captured (the arena was re-laid after the warm-up?)")
+            a = self.arena
+            self._table = ops.trust_segments(a.offsets, [p.numel() for p in a.params],
+                                             ops.trust.flags_for(a.params, self.adapt_1d), a.numel, a.device)
+            self._table_layout = (a.offsets, a.param_flat)
+        return self._table
+
+    def _new_state(self) -> torch.Tensor:
+        if self._capturing():
+            raise RuntimeError("optimizer state must be allocated by an eager step before capture")
+        return self.arena.zeros_like_arena()
+
+    @property
+    def trust_ratios(self) -> torch.Tensor:
+        """Last step's ratio per arena parameter (arena order), on the device."""
+        return self._ensure_table().ratio
+
+    def _invalidate_table(self) -> None:
+        self._table = None
+        self._table_layout = None
+
+
+class FusedLARS(_TrustOptimizer):
+    """LARS (You, Gitman, Ginsburg 2017) with momentum over the flat arena: per parameter
+    ``ratio = eta ||p|| / (||g|| + wd ||p||)``, ``d = ratio (g + wd p)``, then SGD momentum on d.
+    Parameters with ``ndim <= 1`` get ratio 1 and no weight decay unless ``adapt_1d``."""
+
+    def __init__(self, arena, lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 0.0,
+                 nesterov: bool = False, trust_coefficient: float = 0.001, adapt_1d: bool = False,
+                 params_in_order: Optional[Sequence[torch.Tensor]] = None) -> None:
+        if nesterov and momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum")
+        super().__init__(arena, params_in_order,
+                         dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay,
+                              nesterov=nesterov, maximize=False, foreach=None, differentiable=False,
+                              fused=True, trust_coefficient=trust_coefficient), adapt_1d)
+        self.momentum_buffer: Optional[torch.Tensor] = None
+
+    def arena_state(self) -> List[torch.Tensor]:
+        return [self.momentum_buffer] if self.momentum_buffer is not None else []
+
+    def set_arena_state(self, tensors: Sequence[torch.Tensor]) -> None:
+        self._invalidate_table()
+        if tensors:
+            self.momentum_buffer = tensors[0]
+
+    def step(self, scaler: Optional[DeviceGradScaler] = None, host_factor: float = 1.0,
+             grads_checked: bool = False, shadow: Optional[torch.Tensor] = None,
+             zero_grad: bool = True) -> None:
+        g = self.group
+        table = self._ensure_table()
+        if self.momentum_buffer is None:
+            self.momentum_buffer = self._new_state()
+        scale, found_inf = self._prologue(scaler, host_factor, grads_checked)
+        ops.lars_step(self.arena.param_flat, self.arena.grad_flat, self.momentum_buffer, table, table.ratio,
+                      lr=g["lr"], momentum=g["momentum"], weight_decay=g["weight_decay"],
+                      eta=g["trust_coefficient"], nesterov=g["nesterov"], scale=scale,
+                      host_factor=host_factor, found_inf=found_inf, step=self._step, zero_grad=zero_grad,
+                      shadow=shadow)
+        self._epilogue(scaler, found_inf)
+
+    def state_dict(self) -> Dict[str, Any]:
+        state: Dict[int, Dict[str, Any]] = {}
+        if self.momentum_buffer is not None and float(self._step.item()) > 0:
+            for i, t in enumerate(self._export(self.momentum_buffer)):
+                state[i] = {"momentum_buffer": t}
+        return {"state": state, "param_groups": self._groups_state()}
+
+    def load_state_dict(self, sd: Dict[str, Any]) -> None:
+        for k, v in sd["param_groups"][0].items():
+            if k != "params":
+                self.group[k] = v
+        st = sd.get("state", {})
+        if st:
+            if self.momentum_buffer is None:
+                self.momentum_buffer = self.arena.zeros_like_arena()
+            bufs = [st[i]["momentum_buffer"] if i in st else st[str(i)]["momentum_buffer"]
+                    for i in range(len(self._order))]
+            self._import(self.momentum_buffer, bufs)
+            self._step.fill_(max(1.0, float(self._step.item())))
+
+
+class FusedLAMB(_TrustOptimizer):
+    """LAMB (You et al. 2020) over the flat arena: Adam moments with bias correction,
+    ``u = m_hat / (sqrt(v_hat) + eps) + wd p``, ``p -= lr (||p|| / ||u||) u`` per parameter.
+    Parameters with ``ndim <= 1`` get ratio 1 and no weight decay unless ``adapt_1d``."""
+
+    def __init__(self, arena, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, adapt_1d: bool = False,
+                 params_in_order: Optional[Sequence[torch.Tensor]] = None) -> None:
+        super().__init__(arena, params_in_order,
+                         dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False,
+                              maximize=False, foreach=None, capturable=True, differentiable=False,
+                              fused=True), adapt_1d)
+        self.exp_avg: Optional[torch.Tensor] = None
+        self.exp_avg_sq: Optional[torch.Tensor] = None
+
+    def arena_state(self) -> List[torch.Tensor]:
+        return [self.exp_avg, self.exp_avg_sq] if self.exp_avg is not None else []
+
+    def set_arena_state(self, tensors: Sequence[torch.Tensor]) -> None:
+        self._invalidate_table()
+        if tensors:
+            self.exp_avg, self.exp_avg_sq = tensors
+
+    def step(self, scaler: Optional[DeviceGradScaler] = None, host_factor: float = 1.0,
+             grads_checked: bool = False, shadow: Optional[torch.Tensor] = None,
+             zero_grad: bool = True) -> None:
+        g = self.group
+        table = self._ensure_table()
+        if self.exp_avg is None:
+            self.exp_avg = self._new_state()
+            self.exp_avg_sq = self._new_state()
+        scale, found_inf = self._prologue(scaler, host_factor, grads_checked)
+        b1, b2 = g["betas"]
+        ops.lamb_step(self.arena.param_flat, self.arena.grad_flat, self.exp_avg, self.exp_avg_sq, table,
+                      table.ratio, lr=g["lr"], beta1=b1, beta2=b2, eps=g["eps"],
+                      weight_decay=g["weight_decay"], scale=scale, host_factor=host_factor,
+                      found_inf=found_inf, step=self._step, zero_grad=zero_grad, shadow=shadow)
+        self._epilogue(scaler, found_inf)
+
+    def state_dict(self) -> Dict[str, Any]:
+        state: Dict[int, Dict[str, Any]] = {}
+        if self.exp_avg is not None:
+            step = self._step.detach().reshape(()).clone()
+            for i, (m, v) in enumerate(zip(self._export(self.exp_avg), self._export(self.exp_avg_sq))):
+                state[i] = {"step": step.clone(), "exp_avg": m, "exp_avg_sq": v}
+        return {"state": state, "param_groups": self._groups_state()}
+
+    def load_state_dict(self, sd: Dict[str, Any]) -> None:
+        for k, v in sd["param_groups"][0].items():
+            if k != "params":
+                self.group[k] = tuple(v) if k == "betas" else v
+        st = sd.get("state", {})
+        if st:
+            if self.exp_avg is None:
+                self.exp_avg = self.arena.zeros_like_arena()
+                self.exp_avg_sq = self.arena.zeros_like_arena()
+            get = lambda i: st[i] if i in st else st[str(i)]
+            self._import(self.exp_avg, [get(i)["exp_avg"] for i in range(len(self._order))])
+            self._import(self.exp_avg_sq, [get(i)["exp_avg_sq"] for i in range(len(self._order))])
+            self._step.fill_(float(torch.as_tensor(get(0)["step"]).item()))
+
+
 def build_optimizer(name: str, arena, args, params_in_order=None) -> _FlatOptimizer:
+    if name == "lars":
+        return FusedLARS(arena, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
+                         nesterov=getattr(args, "nesterov", False),
+                         trust_coefficient=getattr(args, "trust_coefficient", 0.001),
+                         adapt_1d=getattr(args, "adapt_1d", False), params_in_order=params_in_order)
+    if name == "lamb":
+        return FusedLAMB(arena, lr=args.lr, betas=getattr(args, "betas", (0.9, 0.999)),
+                         eps=getattr(args, "eps", 1e-8), weight_decay=args.weight_decay,
+                         adapt_1d=getattr(args, "adapt_1d", False), params_in_order=params_in_order)
     if name == "sgd":
         return FusedSGD(arena, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
                         nesterov=getattr(args, "nesterov", False), params_in_order=params_in_order)
