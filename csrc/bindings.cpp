@@ -980,10 +980,11 @@ Tensor bn_apply_aff(Tensor x, Tensor x2, Tensor coef, Tensor coef2, c10::optiona
 }
 
 // Backward of bn_apply_aff + ReLU from dgrad-epilogue partials (dz already masked): {dx, dx2,
-// dgamma, dbeta, dgamma2, dbeta2}.
+// dgamma, dbeta, dgamma2, dbeta2}.  apply = false: the finalize only, {kbuf [6C], None, dgamma, ...}
+// (as bn_fwd_train(..., apply=False): the caller runs the apply, conv1x1_tail_bwd).
 std::vector<Tensor> bn2_bwd_partials(Tensor dz, Tensor x, Tensor x2, c10::optional<Tensor> weight,
                                      c10::optional<Tensor> weight2, Tensor mean, Tensor invstd, Tensor mean2,
-                                     Tensor invstd2, Tensor p1, Tensor p2, Tensor p3, bool want_dparams) {
+                                     Tensor invstd2, Tensor p1, Tensor p2, Tensor p3, bool want_dparams, bool apply) {
   auto [M, C] = bn_rows(x, "x");
   TORCH_CHECK(dz.sizes() == x.sizes() && x2.sizes() == x.sizes() && dz.scalar_type() == x.scalar_type() &&
                   x2.scalar_type() == x.scalar_type(), "bn2_bwd_partials: shape/dtype mismatch");
@@ -993,7 +994,7 @@ std::vector<Tensor> bn2_bwd_partials(Tensor dz, Tensor x, Tensor x2, c10::option
     TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->dim() == 2 && t->size(0) == C &&
                     t->is_contiguous() && t->sizes() == p1.sizes(), "bn2_bwd_partials: partials must be fp32 [C, chunks]");
   auto fopt = x.options().dtype(at::kFloat);
-  auto dx = at::empty_like(x), dx2 = at::empty_like(x2);
+  Tensor dx = apply ? at::empty_like(x) : Tensor(), dx2 = apply ? at::empty_like(x2) : Tensor();
   Tensor dg = want_dparams ? at::empty({C}, fopt) : Tensor(), db = want_dparams ? at::empty({C}, fopt) : Tensor();
   Tensor dg2 = want_dparams ? at::empty({C}, fopt) : Tensor(), db2 = want_dparams ? at::empty({C}, fopt) : Tensor();
   auto kbuf = at::empty({6 * C}, fopt);
@@ -1004,8 +1005,9 @@ std::vector<Tensor> bn2_bwd_partials(Tensor dz, Tensor x, Tensor x2, c10::option
       f32_param(mean2, C, "mean2"), f32_param(invstd2, C, "invstd2"), p1.data_ptr<float>(), p2.data_ptr<float>(),
       p3.data_ptr<float>(), (int)p1.size(1), want_dparams ? dg.data_ptr<float>() : nullptr,
       want_dparams ? db.data_ptr<float>() : nullptr, want_dparams ? dg2.data_ptr<float>() : nullptr,
-      want_dparams ? db2.data_ptr<float>() : nullptr, dx.data_ptr(), dx2.data_ptr(), kbuf.data_ptr<float>(),
-      cur_stream(x));
+      want_dparams ? db2.data_ptr<float>() : nullptr, apply ? dx.data_ptr() : nullptr,
+      apply ? dx2.data_ptr() : nullptr, kbuf.data_ptr<float>(), cur_stream(x), apply);
+  if (!apply) return {kbuf, Tensor(), dg, db, dg2, db2};
   return {dx, dx2, dg, db, dg2, db2};
 }
 
@@ -1110,9 +1112,11 @@ std::vector<Tensor> bn_bwd(Tensor dy, c10::optional<Tensor> dy2, c10::optional<T
 }
 
 // BN+ReLU backward from statistics partials summed by the consuming conv's dgrad epilogue:
-// {dx, dgamma, dbeta}; the ReLU mask is recomputed from x and coef.
+// {dx, dgamma, dbeta}; the ReLU mask is recomputed from x and coef.  apply = false: the finalize only,
+// {kbuf [3C] = k1 | k2 | k3, dgamma, dbeta} (the caller runs the apply: conv1x1_tail_bwd, bn_bwd_apply_pre).
 std::vector<Tensor> bn_bwd_partials(Tensor dy, Tensor x, c10::optional<Tensor> weight, Tensor mean, Tensor invstd,
-                                    c10::optional<Tensor> coef, Tensor p1, Tensor p2, bool want_dparams, bool from_dz) {
+                                    c10::optional<Tensor> coef, Tensor p1, Tensor p2, bool want_dparams, bool from_dz,
+                                    bool apply) {
   auto [M, C] = bn_rows(x, "x");
   auto [Md, Cd] = bn_rows(dy, "grad_output");
   TORCH_CHECK(M == Md && C == Cd && dy.scalar_type() == x.scalar_type(), "grad_output mismatch");
@@ -1121,7 +1125,7 @@ std::vector<Tensor> bn_bwd_partials(Tensor dy, Tensor x, c10::optional<Tensor> w
               "bn_bwd_partials: partials must be contiguous fp32 [C, chunks]");
   TORCH_CHECK(from_dz || (coef.has_value() && coef->defined()), "bn_bwd_partials: coef needed unless from_dz");
   auto fopt = x.options().dtype(at::kFloat);
-  auto dx = at::empty_like(x);
+  Tensor dx = apply ? at::empty_like(x) : Tensor();
   Tensor dg = want_dparams ? at::empty({C}, fopt) : Tensor();
   Tensor db = want_dparams ? at::empty({C}, fopt) : Tensor();
   auto kbuf = at::empty({3 * C}, fopt);
@@ -1130,9 +1134,79 @@ std::vector<Tensor> bn_bwd_partials(Tensor dy, Tensor x, c10::optional<Tensor> w
                                    f32_param(mean, C, "mean"), f32_param(invstd, C, "invstd"),
                                    f32_param(coef, 2 * C, "coef"), p1.data_ptr<float>(), p2.data_ptr<float>(),
                                    (int)p1.size(1), want_dparams ? dg.data_ptr<float>() : nullptr,
-                                   want_dparams ? db.data_ptr<float>() : nullptr, dx.data_ptr(), kbuf.data_ptr<float>(),
-                                   cur_stream(x), from_dz);
+                                   want_dparams ? db.data_ptr<float>() : nullptr, apply ? dx.data_ptr() : nullptr,
+                                   kbuf.data_ptr<float>(), cur_stream(x), from_dz, apply);
+  if (!apply) return {kbuf, dg, db};
   return {dx, dg, db};
+}
+
+// The materialising apply of a finalize-only bn_bwd_partials / bn2_bwd_partials (dz already masked):
+// dx = k1*dz + k2*(x - mean) + k3 with kbuf = [k1 | k2 | k3] - the pass conv1x1_tail_bwd fuses.
+Tensor bn_bwd_apply_pre(Tensor dz, Tensor x, Tensor mean, Tensor kbuf) {
+  auto [M, C] = bn_rows(x, "x");
+  auto [Md, Cd] = bn_rows(dz, "dz");
+  TORCH_CHECK(M == Md && C == Cd && dz.scalar_type() == x.scalar_type(), "bn_bwd_apply_pre: dz mismatch");
+  auto dx = at::empty_like(x);
+  c10::hip::HIPGuard guard(x.device().index());
+  dpt::launch_bn_bwd_apply_pre(bn_dtype(x), dz.data_ptr(), x.data_ptr(), M, C, f32_param(mean, C, "mean"), nullptr,
+                               f32_param(kbuf, 3 * C, "kbuf"), dx.data_ptr(), cur_stream(x), true);
+  return dx;
+}
+
+// Block-tail backward apply fused into conv3's backward-data (tail_conv3_bwd_kernels.hip): dz, x3 (and
+// x2) are the tail's masked gradient and BatchNorm input(s), kbuf the finalize-only result of
+// bn_bwd_partials / bn2_bwd_partials, w_flipped conv3's flipped weight [C, 4C, 1, 1], bn_x / bn_mean /
+// bn_coef the BN+ReLU that fed conv3.  Returns {dx3, dx_ds | None, dx, p1, p2}, all bit for bit what
+// the apply followed by conv_dgrad_bnstats(dx3, w, 0, bn_x, bn_mean, bn_coef) gives.
+// Refuses (raises) what the kernel does not cover; nothing is written then.
+std::vector<Tensor> conv1x1_tail_bwd(Tensor dz, Tensor x3, c10::optional<Tensor> x2, Tensor kbuf, Tensor mean,
+                                     c10::optional<Tensor> mean2, Tensor w_flipped, Tensor bn_x, Tensor bn_mean,
+                                     Tensor bn_coef) {
+  check_cl_bf16(dz, "dz");
+  check_cl_bf16(x3, "x3");
+  check_cl_bf16(w_flipped, "w_flipped");
+  check_cl_bf16(bn_x, "bn_x");
+  same_16(dz, x3, "conv1x1_tail_bwd");
+  same_16(dz, w_flipped, "conv1x1_tail_bwd");
+  same_16(dz, bn_x, "conv1x1_tail_bwd");
+  TORCH_CHECK(dz.sizes() == x3.sizes(), "conv1x1_tail_bwd: dz / x3 mismatch");
+  const int N = x3.size(0), C4 = x3.size(1), H = x3.size(2), W = x3.size(3);
+  const int64_t M = (int64_t)N * H * W;
+  const int C = w_flipped.size(0);
+  TORCH_CHECK(w_flipped.size(1) == C4 && w_flipped.size(2) == 1 && w_flipped.size(3) == 1,
+              "conv1x1_tail_bwd: w_flipped must be [C, 4C, 1, 1] (a 1x1 / stride-1 / unpadded conv only)");
+  TORCH_CHECK(bn_x.size(0) == N && bn_x.size(1) == C && bn_x.size(2) == H && bn_x.size(3) == W,
+              "conv1x1_tail_bwd: bn_x must match the conv input");
+  const bool two = x2.has_value() && x2->defined();
+  if (two) {
+    check_cl_bf16(*x2, "x2");
+    same_16(dz, *x2, "conv1x1_tail_bwd");
+    TORCH_CHECK(x2->sizes() == x3.sizes() && mean2.has_value() && mean2->defined(), "conv1x1_tail_bwd: x2 / mean2");
+  }
+  const char* why = dpt::tail_conv3_bwd_refusal(M, C4, C);
+  TORCH_CHECK(why == nullptr, "conv1x1_tail_bwd: ", why ? why : "");
+  const float* kp = f32_param(kbuf, (two ? 6 : 3) * (int64_t)C4, "kbuf");
+  const float* mp = f32_param(mean, C4, "mean");
+  const float* mp2 = two ? f32_param(*mean2, C4, "mean2") : nullptr;
+  const float* bm = f32_param(bn_mean, C, "bn_mean");
+  const float* bc = f32_param(bn_coef, 2 * C, "bn_coef");
+  auto dx3 = at::empty_like(x3);
+  Tensor dx_ds = two ? at::empty_like(*x2) : Tensor();
+  auto dx = at::empty({N, C, H, W}, dz.options().memory_format(at::MemoryFormat::ChannelsLast));
+  const int64_t mt = dpt::conv_m_tiles(M);
+  auto p1 = at::empty({C, mt}, dz.options().dtype(at::kFloat));
+  auto p2 = at::empty({C, mt}, dz.options().dtype(at::kFloat));
+  c10::hip::HIPGuard guard(dz.device().index());
+  dpt::launch_tail_conv3_bwd(is_f16(dz), reinterpret_cast<const uint16_t*>(dz.data_ptr()),
+                             reinterpret_cast<const uint16_t*>(x3.data_ptr()),
+                             two ? reinterpret_cast<const uint16_t*>(x2->data_ptr()) : nullptr, kp, mp, mp2,
+                             reinterpret_cast<const uint16_t*>(w_flipped.data_ptr()),
+                             reinterpret_cast<uint16_t*>(dx3.data_ptr()),
+                             two ? reinterpret_cast<uint16_t*>(dx_ds.data_ptr()) : nullptr,
+                             reinterpret_cast<const uint16_t*>(bn_x.data_ptr()), bm, bc,
+                             reinterpret_cast<uint16_t*>(dx.data_ptr()), p1.data_ptr<float>(), p2.data_ptr<float>(), M,
+                             C4, C, cur_stream(dz));
+  return {dx3, dx_ds, dx, p1, p2};
 }
 
 std::vector<Tensor> maxpool_fwd(Tensor x, int64_t k, int64_t stride, int64_t pad, c10::optional<Tensor> bn_coef) {
@@ -1498,7 +1572,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "why conv1x1_tail_fwd refuses this shape (None: it takes it)");
   m.def("bn2_bwd_partials", &bn2_bwd_partials, py::arg("dz"), py::arg("x"), py::arg("x2"), py::arg("weight"),
         py::arg("weight2"), py::arg("mean"), py::arg("invstd"), py::arg("mean2"), py::arg("invstd2"), py::arg("p1"),
-        py::arg("p2"), py::arg("p3"), py::arg("want_dparams"));
+        py::arg("p2"), py::arg("p3"), py::arg("want_dparams"), py::arg("apply") = true);
+  m.def("bn_bwd_apply_pre", &bn_bwd_apply_pre, py::arg("dz"), py::arg("x"), py::arg("mean"), py::arg("kbuf"));
+  m.def("conv1x1_tail_bwd", &conv1x1_tail_bwd, py::arg("dz"), py::arg("x3"), py::arg("x2"), py::arg("kbuf"),
+        py::arg("mean"), py::arg("mean2"), py::arg("w_flipped"), py::arg("bn_x"), py::arg("bn_mean"), py::arg("bn_coef"));
+  m.def("conv1x1_tail_bwd_refusal", [](int64_t M, int64_t C4, int64_t C) -> py::object {
+          const char* why = dpt::tail_conv3_bwd_refusal(M, C4, C);
+          return why ? py::object(py::str(why)) : py::object(py::none());
+        }, py::arg("M"), py::arg("C4"), py::arg("C"),
+        "why conv1x1_tail_bwd refuses this shape (None: it takes it)");
   m.def("bn_bwd", &bn_bwd, py::arg("grad_output"), py::arg("grad_output2"), py::arg("y"), py::arg("x"),
         py::arg("weight"), py::arg("mean"), py::arg("invstd"), py::arg("relu"), py::arg("want_dz"),
         py::arg("want_dparams"), py::arg("coef") = py::none());
@@ -1577,7 +1659,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("wgrad_reduce") = nullptr);
   m.def("bn_bwd_partials", &bn_bwd_partials, py::arg("grad_output"), py::arg("x"), py::arg("weight"), py::arg("mean"),
         py::arg("invstd"), py::arg("coef"), py::arg("p1"), py::arg("p2"), py::arg("want_dparams"),
-        py::arg("from_dz") = false);
+        py::arg("from_dz") = false, py::arg("apply") = true);
   m.def("conv_dgrad_s2", &conv_dgrad_s2, py::arg("grad_output"), py::arg("w"), py::arg("pad"), py::arg("H"),
         py::arg("W"), py::arg("bn_x") = py::none(), py::arg("bn_mean") = py::none(), py::arg("bn_coef") = py::none(),
         py::arg("wgrad_reduce") = nullptr, py::arg("compact") = false);

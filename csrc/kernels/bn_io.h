@@ -1,11 +1,19 @@
 // 8-element vector I/O for the three activation dtypes of the fused BatchNorm kernels
 // (bn_kernels.hip) - shared with the kernels that redo the BN apply arithmetic bit for bit
-// (tail_conv1_kernels.hip).
+// (tail_conv1_kernels.hip, tail_conv3_bwd_kernels.hip).
 #pragma once
 
 #include "common.h"
 
 namespace dpt {
+
+// The backward apply's dx = k1*dz + k2*(x - mean) + k3 with its contraction written out (the product
+// k2*(x - mean) rounded, k1*dz fused onto it, k3 added: what the compiler made of the plain
+// expression): bn_bwd_apply_kernel, bn_bwd_apply2_kernel and tail_conv3_bwd_kernel all call this, so
+// their bits agree by construction and not by what a compiler version happens to fuse.
+__device__ __forceinline__ float bn_bwd_dx(float k1, float dz, float k2, float x, float mean, float k3) {
+  return __builtin_fmaf(k1, dz, k2 * (x - mean)) + k3;
+}
 
 // ---- 8-element vector I/O for the three activation dtypes ----------------------------------
 struct BF16 {

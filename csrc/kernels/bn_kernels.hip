@@ -406,7 +406,7 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_kernel(const void* __rest
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       float dz = (FROM_DZ || !RELU || m[k]) ? g[k] : 0.0f;
-      o[k] = c1[k] * dz + c2[k] * (xv[k] - mu[k]) + c3[k];
+      o[k] = bn_bwd_dx(c1[k], dz, c2[k], xv[k], mu[k], c3[k]);
     }
     IO::store8(dx, r * C + cg * 8, o);
   }
@@ -444,8 +444,8 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply2_kernel(const void* __res
     IO::load8(x2, off, x2v);
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-      o[q] = c1[q] * g[q] + c2[q] * (xv[q] - mu[q]) + c3[q];
-      o2[q] = e1[q] * g[q] + e2[q] * (x2v[q] - mu2[q]) + e3[q];
+      o[q] = bn_bwd_dx(c1[q], g[q], c2[q], xv[q], mu[q], c3[q]);
+      o2[q] = bn_bwd_dx(e1[q], g[q], e2[q], x2v[q], mu2[q], e3[q]);
     }
     IO::store8(dx, off, o);
     IO::store8(dx2, off, o2);
@@ -658,14 +658,14 @@ void launch_bn_bwd_apply_pre(int dtype, const void* dy, const void* x, int64_t M
 void launch_bn_bwd_from_partials(int dtype, const void* dy, const void* x, int64_t M, int64_t C, const float* gamma,
                                  const float* mean, const float* invstd, const float* coef, const float* p1,
                                  const float* p2, int chunks, float* dgamma, float* dbeta, void* dx, float* kbuf,
-                                 hipStream_t s, bool from_dz) {
+                                 hipStream_t s, bool from_dz, bool apply) {
   BnGeometry g = bn_geometry(M, C);
   float* k1 = kbuf;
   float* k2 = k1 + C;
   float* k3 = k2 + C;
   dim3 bl(kBlock);
   launch_bn_bwd_fin(make_bn_bwd_fin(p1, p2, chunks, (int)C, M, gamma, invstd, dgamma, dbeta, k1, k2, k3, -1), s);
-  launch_bn_bwd_apply_pre(dtype, dy, x, M, C, mean, coef, kbuf, dx, s, from_dz);
+  if (apply) launch_bn_bwd_apply_pre(dtype, dy, x, M, C, mean, coef, kbuf, dx, s, from_dz);
 }
 
 void launch_bn_apply_aff(int dtype, const void* x, const void* x2, void* y, int64_t M, int64_t C, const float* a,
@@ -686,7 +686,7 @@ void launch_bn2_bwd_from_partials(int dtype, const void* dz, const void* x, cons
                                   const float* gamma, const float* mean, const float* invstd, const float* gamma2,
                                   const float* mean2, const float* invstd2, const float* p1, const float* p2,
                                   const float* p3, int chunks, float* dgamma, float* dbeta, float* dgamma2,
-                                  float* dbeta2, void* dx, void* dx2, float* kbuf, hipStream_t s) {
+                                  float* dbeta2, void* dx, void* dx2, float* kbuf, hipStream_t s, bool apply) {
   BnGeometry g = bn_geometry(M, C);
   float* k = kbuf;          // [3C] tail
   float* j = kbuf + 3 * C;  // [3C] downsample
@@ -696,6 +696,7 @@ void launch_bn2_bwd_from_partials(int dtype, const void* dz, const void* x, cons
       make_bn_bwd_fin(p1, p3, chunks, (int)C, M, gamma2, invstd2, dgamma2, dbeta2, j, j + C, j + 2 * C, -1);
   if (!g_bn_skip_finalize)
     hipLaunchKernelGGL(bn_bwd_finalize2_kernel, dim3((unsigned)(f1.blocks + f2.blocks)), dim3(kBlock), 0, s, f1, f2);
+  if (!apply) return;
   dim3 ga(g.apply_blocks * 2 > kBnBwdApplyMax ? kBnBwdApplyMax : g.apply_blocks * 2);
   switch (dtype) {
     case 0: hipLaunchKernelGGL(bn_bwd_apply2_kernel<F32>, ga, bl, 0, s, dz, x, x2, mean, mean2, k, j, dx, dx2, M, (int)C, kBnReverse); break;

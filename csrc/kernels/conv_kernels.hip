@@ -2738,6 +2738,22 @@ void launch_conv_dgrad_bnstats(const uint16_t* dy, const uint16_t* wt, uint16_t*
   else run(Opts<kBnb>{});
 }
 
+// Whether launch_conv_dgrad_bnstats with the plain BNB epilogue (no residual) on a 1x1 conv, M rows,
+// C output channels and K = Cout reduction, runs conv_fwd_kernel<128, BN, 1, LDSEPI, BNB> unsplit on
+// the plain grid - eagerly and under graph capture: nullptr then, else which other path it takes.
+// Asks the policy functions of that launch in its order; decides nothing itself.
+const char* conv_dgrad_bnb_plain_tile_refusal(int64_t M, int C, int64_t K) {
+  if (conv_fwd_splits_for(M, C, K, false) != 1 || conv_fwd_splits_for(M, C, K, true) != 1)
+    return "the split-K policy splits this backward-data";
+  if (fwd_variant() != 0) return "a forced kernel variant";
+  if (conv_big_auto(M, C, K, 1) != 0) return "the backward-data takes an 8-wave tile";
+  if (g_conv_breg & 2) return "the backward-data keeps its B operand in registers";
+  const int bn = C % 128 == 0 ? 128 : 64;
+  if (g_conv_sk && conv_sk_blocks((int64_t)conv_m_tiles(M) * (C / bn), (int)(K / conv::BK), bn, g_conv_sk) > 0)
+    return "the backward-data runs the stream-K grid";
+  return nullptr;
+}
+
 // A Linear's backward-data with the exact-GELU backward of its input fused into the epilogue
 // (ViT's fc2 -> GELU -> fc1 chain): gu[t, i] = (sum_o dy[t, o] wt[i, o]) * gelu'(u[t, i] + bias[i])
 // and bp1[i][mt] = the column sums of gu over 128-row tile mt (the bias gradient's partials).

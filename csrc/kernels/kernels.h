@@ -89,17 +89,19 @@ void launch_bn_fwd_from_partials(int dtype, const void* x, const void* res, void
 void launch_bn_bwd_from_partials(int dtype, const void* dy, const void* x, int64_t M, int64_t C, const float* gamma,
                                  const float* mean, const float* invstd, const float* coef, const float* p1,
                                  const float* p2, int chunks, float* dgamma, float* dbeta, void* dx, float* kbuf,
-                                 hipStream_t s, bool from_dz = false);
+                                 hipStream_t s, bool from_dz = false, bool apply = true);
 // y = relu(x*a + b + x2*a2 + b2) (block tail with its downsample BatchNorm folded in)
 void launch_bn_apply_aff(int dtype, const void* x, const void* x2, void* y, int64_t M, int64_t C, const float* a,
                          const float* b, const float* a2, const float* b2, hipStream_t s, uint8_t* mask = nullptr);
 // backward of that: finalize both BNs from dgrad-epilogue partials (p1 shared), one apply pass
-// writing dx and dx2; kbuf: 6C floats
+// writing dx and dx2; kbuf: 6C floats.  apply = false (here and in launch_bn_bwd_from_partials): the
+// finalize only - kbuf = [k1 | k2 | k3] ([j1 | j2 | j3] behind it), dgamma and dbeta; dx / dx2 are
+// not touched (the caller runs the apply itself: tail_conv3_bwd_kernels.hip)
 void launch_bn2_bwd_from_partials(int dtype, const void* dz, const void* x, const void* x2, int64_t M, int64_t C,
                                   const float* gamma, const float* mean, const float* invstd, const float* gamma2,
                                   const float* mean2, const float* invstd2, const float* p1, const float* p2,
                                   const float* p3, int chunks, float* dgamma, float* dbeta, float* dgamma2,
-                                  float* dbeta2, void* dx, void* dx2, float* kbuf, hipStream_t s);
+                                  float* dbeta2, void* dx, void* dx2, float* kbuf, hipStream_t s, bool apply = true);
 void bn_set_skip_finalize(int on);  // measurement only (bench/ab_step.py): skip BN finalize launches
 void launch_bn_apply(int dtype, const void* x, const void* res, void* y, int64_t M, int64_t C,
                      const float* coef_a, const float* coef_b, bool relu, hipStream_t s, uint8_t* mask = nullptr);
@@ -114,6 +116,22 @@ const char* tail_conv1_refusal(int64_t M, int64_t Cin, int64_t Cout);
 void launch_tail_conv1_fwd(bool f16, const uint16_t* x3, const uint16_t* r, const float* coef, const float* coef2,
                            const uint16_t* w, uint16_t* y, uint8_t* mask, uint16_t* x1, float* psum, float* psq,
                            int64_t M, int Cin, int Cout, hipStream_t s);
+// tail_conv3_bwd_kernels.hip: a block tail's backward apply dx3 = k1*dz + k2*(x3 - mean) + k3 (and,
+// with x2, dx_ds = j1*dz + j2*(x2 - mean2) + j3) and conv3's backward-data dx = dx3 wt^T with the BNB
+// epilogue of bn2 (bnx / bn_mean / bn_coef; bp1/bp2 [C][conv_m_tiles(M)]), in one kernel.  dz, x3, x2,
+// dx3, dx_ds [M, C4]; wt [C][C4] (the flipped weight); bnx, dx [M, C]; kbuf = [k1 | k2 | k3] (and
+// [j1 | j2 | j3] behind it) from the finalize.  Every output is bit-equal to launch_bn_bwd_apply_pre
+// (from_dz) / the apply of launch_bn2_bwd_from_partials followed by the unsplit
+// launch_conv_dgrad_bnstats without a residual.
+// tail_conv3_bwd_refusal: nullptr when the kernel takes the shape, else why not (the launch throws it).
+const char* tail_conv3_bwd_refusal(int64_t M, int64_t C4, int64_t C);
+void launch_tail_conv3_bwd(bool f16, const uint16_t* dz, const uint16_t* x3, const uint16_t* x2, const float* kbuf,
+                           const float* mean, const float* mean2, const uint16_t* wt, uint16_t* dx3, uint16_t* dx_ds,
+                           const uint16_t* bnx, const float* bn_mean, const float* bn_coef, uint16_t* dx, float* bp1,
+                           float* bp2, int64_t M, int C4, int C, hipStream_t s);
+// conv_kernels.hip: why launch_conv_dgrad_bnstats (plain BNB epilogue, 1x1, K = Cout) would not run
+// the unsplit 4-wave 128 x BN tile for this shape (nullptr: it would)
+const char* conv_dgrad_bnb_plain_tile_refusal(int64_t M, int C, int64_t K);
 void launch_bn_bwd(int dtype, const void* dy, const void* dy2, const void* y, const void* x, int64_t M,
                    int64_t C, const float* gamma, const float* mean, const float* invstd, const float* coef,
                    float* dgamma, float* dbeta, void* dx, void* dz, float* workspace, bool relu, hipStream_t s);

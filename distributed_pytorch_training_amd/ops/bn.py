@@ -24,6 +24,7 @@ import torch
 import os
 
 from . import native, native_available
+from . import conv as _conv
 from .conv import COMPACT_RES, MASKED_NO_RES, materialize_tail, take_bnb_partials
 
 # Block-tail BN+add+ReLU backward statistics in the consuming conv's dgrad epilogue (see _bwd)
@@ -109,6 +110,8 @@ def _fwd(ctx, x, residual, weight, bias, running_mean, running_var, num_batches,
         # a native conv consuming y sums this BN's backward statistics in its dgrad epilogue
         y._dpt_bn_src = (x, mean, coef)
     ctx.res_slot = res_slot  # our residual input is the identity alias of an earlier block tail
+    # x came from a conv whose backward-data this tail's backward can run (ops/conv.py TAIL_CONV3_BWD_FUSE)
+    ctx.tail_link = links[3] if len(links) > 3 else None
     if own_slot is not None:
         if mask is not None:
             own_slot["mask"] = mask
@@ -116,6 +119,16 @@ def _fwd(ctx, x, residual, weight, bias, running_mean, running_var, num_batches,
         # gradient the next block's tail leaves in own_slot, see _bwd) in its dgrad epilogue
         y._dpt_bn_src = (x, mean, own_slot)
     return y
+
+
+def _apply_from_dz(link, dz, x, weight, mean, invstd, p1, p2, want_params):
+    """``bn_bwd_partials(..., from_dz=True)`` of a block tail: (dx, dgamma, dbeta).  With a link whose
+    conv the fused kernel takes (ops/conv.py TAIL_CONV3_BWD_FUSE), the finalize only, then one kernel
+    that writes dx and also runs that conv's backward-data; dx is filled when this returns either way."""
+    if _conv.tail_bwd_refusal(link, x) is not None:
+        return native().bn_bwd_partials(dz, x, weight, mean, invstd, None, p1, p2, want_params, True)
+    kbuf, dg, db = native().bn_bwd_partials(dz, x, weight, mean, invstd, None, p1, p2, want_params, True, False)
+    return _conv.tail_bwd_apply(link, dz, x, kbuf, mean)[0], dg, db
 
 
 def _bwd(ctx, dy, dy2):
@@ -142,8 +155,8 @@ def _bwd(ctx, dy, dy2):
             if part[2] != dy2.data_ptr():
                 raise RuntimeError("fused block-tail backward: the identity-path gradient folded into the "
                                    "conv's dgrad is not the one autograd delivered (alias used twice?)")
-            dx, dg, db = native().bn_bwd_partials(dy, x, weight, mean, invstd, None, part[0], part[1],
-                                                  bool(want_params), True)
+            dx, dg, db = _apply_from_dz(ctx.tail_link, dy, x, weight, mean, invstd, part[0], part[1],
+                                        bool(want_params))
             if ctx.res_slot is not None:
                 ctx.res_slot["dres"] = dy
             return (dx, dy if want_dz else None, dg if want_params else None, db if want_params else None)
@@ -155,8 +168,8 @@ def _bwd(ctx, dy, dy2):
             # COMPACT_RES: the identity alias fed a 1x1 / stride-2 downsample conv, which handed its
             # compact input gradient to the conv-path consumer and returned None to autograd
             # (ops/conv.py S2_COMPACT_DRES): dy is the whole masked gradient, nothing is missing
-            dx, dg, db = native().bn_bwd_partials(dy, x, weight, mean, invstd, None, part[0], part[1],
-                                                  bool(want_params), True)
+            dx, dg, db = _apply_from_dz(ctx.tail_link, dy, x, weight, mean, invstd, part[0], part[1],
+                                        bool(want_params))
             if ctx.res_slot is not None:
                 ctx.res_slot["dres"] = dy
             return (dx, dy if want_dz else None, dg if want_params else None, db if want_params else None)
@@ -182,7 +195,7 @@ class _BN2AddReLUPair(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, x2, w, b, rm, rv, nb, w2, b2, rm2, rv2, nb2, momentum, eps, momentum2, eps2,
-                partials, partials2, own_slot, defer):
+                partials, partials2, own_slot, defer, tail_link=None):
         C = native()
         ps, pq = partials if partials is not None else (None, None)
         ps2, pq2 = partials2 if partials2 is not None else (None, None)
@@ -197,6 +210,7 @@ class _BN2AddReLUPair(torch.autograd.Function):
         else:
             y = C.bn_apply_aff(x, x2, coef, coef2, mask_out=mask)
         ctx.save_for_backward(x, x2, y, w, w2, mean, invstd, mean2, invstd2)
+        ctx.tail_link = tail_link
         ctx.set_materialize_grads(False)
         if own_slot is not None:
             own_slot["mask"] = mask
@@ -209,7 +223,7 @@ class _BN2AddReLUPair(torch.autograd.Function):
         if dy is None:
             dy, dy2 = dy2, None
         if dy is None:
-            return (None,) * 20
+            return (None,) * 21
         want = [ctx.needs_input_grad[i] for i in (2, 3, 7, 8)]
         want_params = any(want)
         C = native()
@@ -218,8 +232,15 @@ class _BN2AddReLUPair(torch.autograd.Function):
             if part[2] != dy2.data_ptr():
                 raise RuntimeError("fused block-tail backward: the identity-path gradient folded into the "
                                    "conv's dgrad is not the one autograd delivered (alias used twice?)")
-            dx, dx2, dg, db, dg2, db2 = C.bn2_bwd_partials(dy, x, x2, w, w2, mean, invstd, mean2, invstd2,
-                                                           part[0], part[1], part[3], bool(want_params))
+            if _conv.tail_bwd_refusal(ctx.tail_link, x) is None:
+                # the finalize only, then one kernel writes dx and dx2 and runs conv3's backward-data
+                # (ops/conv.py TAIL_CONV3_BWD_FUSE)
+                kbuf, _, dg, db, dg2, db2 = C.bn2_bwd_partials(dy, x, x2, w, w2, mean, invstd, mean2, invstd2,
+                                                               part[0], part[1], part[3], bool(want_params), False)
+                dx, dx2 = _conv.tail_bwd_apply(ctx.tail_link, dy, x, kbuf, mean, x2, mean2)
+            else:
+                dx, dx2, dg, db, dg2, db2 = C.bn2_bwd_partials(dy, x, x2, w, w2, mean, invstd, mean2, invstd2,
+                                                               part[0], part[1], part[3], bool(want_params))
         else:
             if part is not None:
                 raise RuntimeError("fused block-tail backward: partials without the downsample statistic")
@@ -229,7 +250,7 @@ class _BN2AddReLUPair(torch.autograd.Function):
                                         bool(want_params), None)
         g = [dg, db, dg2, db2]
         g = [t if (want_params and want[i]) else None for i, t in enumerate(g)]
-        return (dx, dx2, g[0], g[1], None, None, None, g[2], g[3]) + (None,) * 11
+        return (dx, dx2, g[0], g[1], None, None, None, g[2], g[3]) + (None,) * 12
 
 
 def _tail_defer(x, own_slot, consumer):
@@ -274,7 +295,8 @@ def bn2_add_relu_train(x, bn, x2, bn2, consumer=None):
     defer = _tail_defer(x, own_slot, consumer)
     out = _BN2AddReLUPair.apply(x, x2, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                 bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var, bn2.num_batches_tracked,
-                                bn.momentum, bn.eps, bn2.momentum, bn2.eps, partials, partials2, own_slot, defer)
+                                bn.momentum, bn.eps, bn2.momentum, bn2.eps, partials, partials2, own_slot, defer,
+                                x.__dict__.get("_dpt_tail_link"))
     if own_slot is not None:
         out[1]._dpt_res_slot = own_slot
     if defer is not None:
@@ -306,7 +328,7 @@ def bn_act_train(x: torch.Tensor, residual: Optional[torch.Tensor], weight, bias
     fn = _BNActTrainPair if pair else _BNActTrain
     defer = _tail_defer(x, own_slot, consumer)
     out = fn.apply(x, residual, weight, bias, running_mean, running_var, num_batches, momentum, eps, relu,
-                   partials, (own_slot, res_slot, defer))
+                   partials, (own_slot, res_slot, defer, x.__dict__.get("_dpt_tail_link")))
     if own_slot is not None:
         out[1]._dpt_res_slot = own_slot
     if defer is not None:

@@ -50,6 +50,11 @@ S2_COMPACT_DRES = os.environ.get("DPT_S2_COMPACT_DRES", "1") != "0"
 # Backward-weight before backward-data, its split-K reduce run by extra blocks in the
 # backward-data launch's tail (conv_wgrad_deferred / wgrad_reduce=): no reduce launch of its own
 WGRAD_REDUCE_FUSE = os.environ.get("DPT_WGRAD_REDUCE_FUSE", "1") != "0"
+# A bottleneck tail's backward apply also runs conv3's backward-data (one output-channel tile: 64 or
+# 128 channels, ResNet-50's layer1 / layer2 conv3s; csrc/kernels/tail_conv3_bwd_kernels.hip): the tail
+# writes dx3 and conv3's input gradient in one kernel and leaves the latter for conv3's backward, which
+# then launches no backward-data - dx3 is not read back from HBM a second time.  0 = the two kernels.
+TAIL_CONV3_BWD_FUSE = os.environ.get("DPT_TAIL_CONV3_BWD_FUSE", "1") != "0"
 # The im2col stem path is correct but measured slower than MIOpen on ResNet-50's 7x7/2 stem at
 # batch 256 (the [3.2M x 192] bf16 patch matrix is 1.2 GB written and read twice): opt-in only.
 STEM_ENABLED = os.environ.get("DPT_NATIVE_STEM", "0") == "1"
@@ -121,9 +126,13 @@ def _backward(ctx, dy):
     dy = _cl(dy.to(x.dtype))
     s, p = ctx.stride, ctx.pad
     dx = dw = red = None
+    # the tail that produced dy may already have run this conv's backward-data (TAIL_CONV3_BWD_FUSE)
+    link = getattr(ctx, "tail_link", None)
+    stash = _take_tail_stash(link, dy, w) if (link is not None and TAIL_CONV3_BWD_FUSE) else None
     e0 = _mark()
     if ctx.needs_input_grad[1]:
-        if ctx.needs_input_grad[0] and WGRAD_REDUCE_FUSE:
+        # (a taken stash: no backward-data launch will carry the reduce, so it is not deferred)
+        if ctx.needs_input_grad[0] and WGRAD_REDUCE_FUSE and stash is None:
             dw, red = native().conv_wgrad_deferred(dy, x, list(w.shape), s, p)
         else:
             dw = native().conv_wgrad(dy, x, list(w.shape), s, p, False)
@@ -145,7 +154,12 @@ def _backward(ctx, dy):
             if compact and not (src is not None and len(src) == 3 and _is_compact_of(slot.get("dres"), x)):
                 raise RuntimeError("fused block-tail backward: a downsample conv handed over a compact "
                                    "identity-path gradient that this conv's backward-data cannot fold")
-        if src is not None and not isinstance(src[2], dict):  # BN+ReLU: (x, mean, coef)
+        if src is not None and not isinstance(src[2], dict) and stash is not None:
+            # the tail's backward formed dy and this gradient in one kernel
+            dx, p1, p2 = stash
+            _put_bnb(dx, p1, p2, None, None)
+            variant = "taken-from-tail"   # (the launch was noted as tail-bwd-apply+dgrad by the tail)
+        elif src is not None and not isinstance(src[2], dict):  # BN+ReLU: (x, mean, coef)
             bn_x, bn_mean, bn_coef = src
             dx, p1, p2, _ = native().conv_dgrad_bnstats(dy, w, p, bn_x, bn_mean, bn_coef, w_flipped=wt,
                                                         wgrad_reduce=red)
@@ -216,6 +230,9 @@ def reset_side_channels() -> None:
     """New step generation: forget every BN-backward hand-over not consumed so far."""
     _GEN[0] += 1
     _BNB_PARTIALS.clear()
+    for link in _TAIL_STASHED.values():
+        link.pop("stash", None)
+    _TAIL_STASHED.clear()
 
 
 def _put_bnb(dx, p1, p2, dres_ptr, p3) -> None:
@@ -249,6 +266,87 @@ def _flipped(w: torch.Tensor):
         pend.clear()
         wt = _FLIP["done"][key]
     return wt
+
+
+# ---- a block tail's backward apply fused with conv3's backward-data (TAIL_CONV3_BWD_FUSE) ----------
+# conv3's forward leaves a link dict {"w", "wv", "bn_src"} on its output x3 and on its own ctx.  The
+# tail's backward (ops/bn.py) finds it through x3, launches the fused kernel itself - it never returns
+# an unfilled dx3 - and stashes conv3's input gradient in the link; conv3's backward takes the stash
+# when the dy autograd hands it is that very dx3, unmodified, in the same step generation.
+_TAIL_STASHED = {}   # id -> link holding a stash (dropped by reset_side_channels)
+
+
+def _tail_link(x, w, stride, pad, out_hw, bn_src):
+    """The link of an eligible conv3: native 1x1 / stride 1 / unpadded with statistics output whose
+    input comes from a fused BN+ReLU (``bn_src = (x, mean, coef)``), else None."""
+    if not (TAIL_CONV3_BWD_FUSE and BN_BWD_FUSE and torch.is_grad_enabled() and x.requires_grad):
+        return None
+    if not (int(stride) == 1 and int(pad) == 0 and tuple(out_hw) == (0, 0) and w.shape[2] == 1 and w.shape[3] == 1):
+        return None
+    if bn_src is None or len(bn_src) != 3 or isinstance(bn_src[2], dict):
+        return None
+    return {"w": w, "wv": w._version, "bn_src": bn_src}
+
+
+def tail_bwd_refusal(link, x3):
+    """Why the tail on ``x3`` cannot run the linked conv3's backward-data (None: it can)."""
+    if not TAIL_CONV3_BWD_FUSE:
+        return "switched off"
+    if link is None:
+        return "no link"
+    w = link["w"]
+    if w._version != link["wv"]:
+        return "the weight changed since the forward"
+    if x3.dtype not in _DT16 or w.dtype != x3.dtype or tuple(w.shape) != (x3.shape[1], link["bn_src"][0].shape[1], 1, 1):
+        return "operand types or shapes"
+    return native().conv1x1_tail_bwd_refusal(x3.numel() // x3.shape[1], x3.shape[1], w.shape[1])
+
+
+def tail_bwd_apply(link, dz, x3, kbuf, mean, x2=None, mean2=None):
+    """(dx3, dx_ds | None) of a tail whose finalize left ``kbuf``, filled when this returns: the fused
+    launch, or - only when the binding itself refuses the launch after all - the apply pass(es) the
+    finalize was for, noted as ``tail-bwd-refused``.  Any other error (layout, memory, device) is raised."""
+    try:
+        return tail_bwd_launch(link, dz, x3, kbuf, mean, x2, mean2)
+    except RuntimeError as e:
+        if "conv1x1_tail_bwd: " not in str(e) and "tail_conv3_bwd: " not in str(e):
+            raise
+    e0 = _mark()
+    c4 = x3.shape[1]
+    dx3 = native().bn_bwd_apply_pre(dz, x3, mean, kbuf[:3 * c4])
+    dx_ds = None if x2 is None else native().bn_bwd_apply_pre(dz, x2, mean2, kbuf[3 * c4:])
+    _note("dgrad", link["bn_src"][0], link["w"], 1, 0, "tail-bwd-refused", e0)
+    return dx3, dx_ds
+
+
+def tail_bwd_launch(link, dz, x3, kbuf, mean, x2=None, mean2=None):
+    """The fused launch for a tail whose finalize left ``kbuf``: (dx3, dx_ds | None), both filled;
+    conv3's input gradient and bn2's statistics wait in the link for conv3's backward."""
+    w = link["w"]
+    wt = _flipped(w)
+    if wt is None:   # no per-step flip cache (outside the trainer)
+        wt = native().conv_wt_flip_multi([w])[0]
+    bn_x, bn_mean, bn_coef = link["bn_src"]
+    e0 = _mark()
+    dx3, dx_ds, dx, p1, p2 = native().conv1x1_tail_bwd(dz, x3, x2, kbuf, mean, mean2, wt, bn_x, bn_mean, bn_coef)
+    link["stash"] = (dx3.data_ptr(), dx3._version, _GEN[0], tuple(dx3.shape), w._version, dx, p1, p2)
+    _TAIL_STASHED[id(link)] = link
+    _note("dgrad", bn_x, w, 1, 0, "tail-bwd-apply+dgrad", e0)
+    return dx3, dx_ds
+
+
+def _take_tail_stash(link, dy, w):
+    """(dx, p1, p2) the tail's backward left for the conv whose output gradient is ``dy``, once; None
+    when there is none or it was made for another tensor, version, step generation or weight."""
+    ent = link.pop("stash", None)
+    if ent is None:
+        return None
+    _TAIL_STASHED.pop(id(link), None)
+    ptr, ver, gen, shape, wv, dx, p1, p2 = ent
+    if (ptr != dy.data_ptr() or ver != dy._version or gen != _GEN[0] or shape != tuple(dy.shape)
+            or wv != w._version or link["w"].data_ptr() != w.data_ptr()):
+        return None
+    return dx, p1, p2
 
 
 def _is_compact_of(dres, x) -> bool:
@@ -314,7 +412,7 @@ def _tail_fwd(x, w, stride, pad, out_hw, pending):
 
 class _ConvStats(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, stride: int, pad: int, out_hw, bn_src, res_slot, compact_dres, pending):
+    def forward(ctx, x, w, stride: int, pad: int, out_hw, bn_src, res_slot, compact_dres, pending, link=None):
         e0 = _mark()
         fused = _tail_fwd(x, w, stride, pad, out_hw, pending) if pending is not None else None
         if fused is not None:
@@ -326,13 +424,14 @@ class _ConvStats(torch.autograd.Function):
         ctx.save_for_backward(x, w)
         ctx.stride, ctx.pad, ctx.bn_src, ctx.res_slot = stride, pad, bn_src, res_slot
         ctx.compact_dres = compact_dres
+        ctx.tail_link = link
         ctx.mark_non_differentiable(ps, pq)
         ctx.set_materialize_grads(False)  # no zero-filled gradients for the statistics outputs
         return y, ps, pq
 
     @staticmethod
     def backward(ctx, dy, _dps, _dpq):
-        return _backward(ctx, dy) + (None,) * 7
+        return _backward(ctx, dy) + (None,) * 8
 
 
 def conv2d(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, bn_stats: bool = False,
@@ -369,9 +468,12 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, bn_stats: bo
                         and tuple(out_hw) == (0, 0) and res_slot is not None and res_slot.get("fold_s2"))
     if not bn_stats:
         return _Conv.apply(x, w, int(stride), int(pad), tuple(out_hw), bn_src, res_slot, compact_dres)
+    link = _tail_link(x, w, stride, pad, out_hw, bn_src)
     y, ps, pq = _ConvStats.apply(x, w, int(stride), int(pad), tuple(out_hw), bn_src, res_slot, compact_dres,
-                                 pending)
+                                 pending, link)
     y._dpt_bn_partials = (ps, pq)
+    if link is not None:
+        y._dpt_tail_link = link
     if pending is not None:  # fused or not, y is the result of this conv on the filled x
         pending["conv"] = (w, int(stride), int(pad), True, y)
     return y
