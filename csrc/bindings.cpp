@@ -1063,11 +1063,20 @@ std::vector<Tensor> conv1x1_tail_fwd(Tensor x3, Tensor r, Tensor coef, c10::opti
   auto ps = at::empty({Cout, mt}, x3.options().dtype(at::kFloat));
   auto pq = at::empty({Cout, mt}, x3.options().dtype(at::kFloat));
   c10::hip::HIPGuard guard(x3.device().index());
-  dpt::launch_tail_conv1_fwd(is_f16(x3), reinterpret_cast<const uint16_t*>(x3.data_ptr()),
-                             reinterpret_cast<const uint16_t*>(r.data_ptr()), a, a2,
-                             reinterpret_cast<const uint16_t*>(w.data_ptr()), reinterpret_cast<uint16_t*>(y_out.data_ptr()),
-                             mp, reinterpret_cast<uint16_t*>(x1.data_ptr()), ps.data_ptr<float>(), pq.data_ptr<float>(), M,
-                             C, Cout, cur_stream(x3));
+  dpt::TailConv1Args t;
+  t.x3 = reinterpret_cast<const uint16_t*>(x3.data_ptr());
+  t.r = reinterpret_cast<const uint16_t*>(r.data_ptr());
+  t.coef = a;
+  t.coef2 = a2;
+  t.w = reinterpret_cast<const uint16_t*>(w.data_ptr());
+  t.y = reinterpret_cast<uint16_t*>(y_out.data_ptr());
+  t.mask = mp;
+  t.x1 = reinterpret_cast<uint16_t*>(x1.data_ptr());
+  t.psum = ps.data_ptr<float>();
+  t.psq = pq.data_ptr<float>();
+  t.M = M;
+  t.Cin = C;
+  dpt::launch_tail_conv1_fwd(is_f16(x3), t, Cout, cur_stream(x3));
   return {x1, ps, pq};
 }
 
@@ -1197,15 +1206,25 @@ std::vector<Tensor> conv1x1_tail_bwd(Tensor dz, Tensor x3, c10::optional<Tensor>
   auto p1 = at::empty({C, mt}, dz.options().dtype(at::kFloat));
   auto p2 = at::empty({C, mt}, dz.options().dtype(at::kFloat));
   c10::hip::HIPGuard guard(dz.device().index());
-  dpt::launch_tail_conv3_bwd(is_f16(dz), reinterpret_cast<const uint16_t*>(dz.data_ptr()),
-                             reinterpret_cast<const uint16_t*>(x3.data_ptr()),
-                             two ? reinterpret_cast<const uint16_t*>(x2->data_ptr()) : nullptr, kp, mp, mp2,
-                             reinterpret_cast<const uint16_t*>(w_flipped.data_ptr()),
-                             reinterpret_cast<uint16_t*>(dx3.data_ptr()),
-                             two ? reinterpret_cast<uint16_t*>(dx_ds.data_ptr()) : nullptr,
-                             reinterpret_cast<const uint16_t*>(bn_x.data_ptr()), bm, bc,
-                             reinterpret_cast<uint16_t*>(dx.data_ptr()), p1.data_ptr<float>(), p2.data_ptr<float>(), M,
-                             C4, C, cur_stream(dz));
+  dpt::TailConv3BwdArgs t;
+  t.dz = reinterpret_cast<const uint16_t*>(dz.data_ptr());
+  t.x3 = reinterpret_cast<const uint16_t*>(x3.data_ptr());
+  t.x2 = two ? reinterpret_cast<const uint16_t*>(x2->data_ptr()) : nullptr;
+  t.k = kp;
+  t.mean = mp;
+  t.mean2 = mp2;
+  t.wt = reinterpret_cast<const uint16_t*>(w_flipped.data_ptr());
+  t.dx3 = reinterpret_cast<uint16_t*>(dx3.data_ptr());
+  t.dx_ds = two ? reinterpret_cast<uint16_t*>(dx_ds.data_ptr()) : nullptr;
+  t.bnx = reinterpret_cast<const uint16_t*>(bn_x.data_ptr());
+  t.bn_mean = bm;
+  t.bn_coef = bc;
+  t.dx = reinterpret_cast<uint16_t*>(dx.data_ptr());
+  t.bp1 = p1.data_ptr<float>();
+  t.bp2 = p2.data_ptr<float>();
+  t.M = M;
+  t.C4 = C4;
+  dpt::launch_tail_conv3_bwd(is_f16(dz), t, C, cur_stream(dz));
   return {dx3, dx_ds, dx, p1, p2};
 }
 

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace dpt {
 
 constexpr int kBlock = 256;         // 4 waves of 64
@@ -24,6 +26,14 @@ __host__ inline int grid_for(int64_t n_vec, int unroll) {
   if (g < 1) g = 1;
   if (g > kMaxBlocks) g = kMaxBlocks;
   return (int)g;
+}
+
+// A run-time bool as a compile-time constant: fn(std::true_type{}) or fn(std::false_type{}).  Both
+// sides are instantiated - only for choices whose both kernels exist.
+template <class Fn>
+__host__ inline void with_bool(bool b, Fn&& fn) {
+  if (b) fn(std::true_type{});
+  else fn(std::false_type{});
 }
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t b) {

@@ -2280,14 +2280,6 @@ static constexpr unsigned opt(bool on, unsigned f) { return on ? f : 0u; }
 template <unsigned F>
 using Opts = std::integral_constant<unsigned, F>;
 
-// A run-time bool as a compile-time constant: fn(std::true_type{}) or fn(std::false_type{}).  Both
-// sides are instantiated - only for choices whose both kernels exist.
-template <class Fn>
-static void with_bool(bool b, Fn&& fn) {
-  if (b) fn(std::true_type{});
-  else fn(std::false_type{});
-}
-
 template <int BMT, int BN, int STAGES, unsigned F, int NT = conv::kThreads, int HB = 1>
 static void launch_fwd_kernel(dim3 grid, hipStream_t s, const ConvFwdArgs& a) {
   hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, STAGES, has(F, kLdsEpi), has(F, kBkn), has(F, kStats), has(F, kBnb),

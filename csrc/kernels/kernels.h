@@ -113,9 +113,21 @@ void launch_bn_apply(int dtype, const void* x, const void* res, void* y, int64_t
 // launch_bn_apply / launch_bn_apply_aff followed by the unsplit launch_conv_fwd.
 // tail_conv1_refusal: nullptr when the kernel takes the shape, else why not (the launch throws it).
 const char* tail_conv1_refusal(int64_t M, int64_t Cin, int64_t Cout);
-void launch_tail_conv1_fwd(bool f16, const uint16_t* x3, const uint16_t* r, const float* coef, const float* coef2,
-                           const uint16_t* w, uint16_t* y, uint8_t* mask, uint16_t* x1, float* psum, float* psq,
-                           int64_t M, int Cin, int Cout, hipStream_t s);
+struct TailConv1Args {
+  const uint16_t* x3 = nullptr;   // [M, Cin] the tail BatchNorm's input
+  const uint16_t* r = nullptr;    // [M, Cin] the residual, or (AFF) the downsample BatchNorm's input
+  const float* coef = nullptr;    // [a | b], 2 * Cin
+  const float* coef2 = nullptr;   // [a2 | b2] (AFF)
+  const uint16_t* w = nullptr;    // [Cout][Cin]
+  uint16_t* y = nullptr;          // [M, Cin]
+  uint8_t* mask = nullptr;        // [M, Cin / 8]
+  uint16_t* x1 = nullptr;         // [M, Cout]
+  float* psum = nullptr;          // [Cout][m_tiles]
+  float* psq = nullptr;
+  int64_t M = 0;
+  int Cin = 0, m_tiles = 0, rev = 0;  // m_tiles, rev: the launch's
+};
+void launch_tail_conv1_fwd(bool f16, TailConv1Args a, int Cout, hipStream_t s);
 // tail_conv3_bwd_kernels.hip: a block tail's backward apply dx3 = k1*dz + k2*(x3 - mean) + k3 (and,
 // with x2, dx_ds = j1*dz + j2*(x2 - mean2) + j3) and conv3's backward-data dx = dx3 wt^T with the BNB
 // epilogue of bn2 (bnx / bn_mean / bn_coef; bp1/bp2 [C][conv_m_tiles(M)]), in one kernel.  dz, x3, x2,
@@ -125,10 +137,27 @@ void launch_tail_conv1_fwd(bool f16, const uint16_t* x3, const uint16_t* r, cons
 // launch_conv_dgrad_bnstats without a residual.
 // tail_conv3_bwd_refusal: nullptr when the kernel takes the shape, else why not (the launch throws it).
 const char* tail_conv3_bwd_refusal(int64_t M, int64_t C4, int64_t C);
-void launch_tail_conv3_bwd(bool f16, const uint16_t* dz, const uint16_t* x3, const uint16_t* x2, const float* kbuf,
-                           const float* mean, const float* mean2, const uint16_t* wt, uint16_t* dx3, uint16_t* dx_ds,
-                           const uint16_t* bnx, const float* bn_mean, const float* bn_coef, uint16_t* dx, float* bp1,
-                           float* bp2, int64_t M, int C4, int C, hipStream_t s);
+struct TailConv3BwdArgs {
+  const uint16_t* dz = nullptr;    // [M, C4] the tail's masked output gradient
+  const uint16_t* x3 = nullptr;    // [M, C4] the tail BatchNorm's input
+  const uint16_t* x2 = nullptr;    // [M, C4] the downsample BatchNorm's input (TWO)
+  const float* k = nullptr;        // [k1 | k2 | k3], 3 * C4 (the finalize's kbuf)
+  const float* mean = nullptr;     // [C4]
+  const float* j = nullptr;        // [j1 | j2 | j3] (TWO): behind k, the launch's
+  const float* mean2 = nullptr;    // [C4] (TWO)
+  const uint16_t* wt = nullptr;    // [C][C4] conv3's flipped weight
+  uint16_t* dx3 = nullptr;         // [M, C4]
+  uint16_t* dx_ds = nullptr;       // [M, C4] (TWO)
+  const uint16_t* bnx = nullptr;   // [M, C] bn2's input
+  const float* bn_mean = nullptr;  // [C]
+  const float* bn_coef = nullptr;  // [a | b], 2 * C
+  uint16_t* dx = nullptr;          // [M, C] conv3's input gradient
+  float* bp1 = nullptr;            // [C][m_tiles]
+  float* bp2 = nullptr;
+  int64_t M = 0;
+  int C4 = 0, m_tiles = 0, rev = 0;  // m_tiles, rev: the launch's
+};
+void launch_tail_conv3_bwd(bool f16, TailConv3BwdArgs a, int C, hipStream_t s);
 // conv_kernels.hip: why launch_conv_dgrad_bnstats (plain BNB epilogue, 1x1, K = Cout) would not run
 // the unsplit 4-wave 128 x BN tile for this shape (nullptr: it would)
 const char* conv_dgrad_bnb_plain_tile_refusal(int64_t M, int C, int64_t K);

@@ -17,10 +17,10 @@
 // [k1 | k2 | k3 | mean] (and [j1 | j2 | j3 | mean2]) sit in LDS, staged once per block.
 //
 // The [M, C] gradient and bp1/bp2 are bit-equal to conv_fwd_kernel<128, BN, 1, LDSEPI, BNB> (STATS
-// off): the same wave tiling (4x1 waves at BN = 64, 2x2 at BN = 128), v_mfma_f32_32x32x16 with ks and
-// kk ascending, the cvt_pk rounding of the epilogue, the mask fma(x, a, b) > 0 from bn2's input, s1/s2
-// summed over a thread's rows in ascending order, shfl_xor CPR..32, waves summed in index order.
-// One 128-row tile per block, plain grid, no inter-block communication.
+// off): the tile, the MFMA order and the rounded LDS image are tail_tile.h's; here, the mask
+// fma(x, a, b) > 0 from bn2's input, s1/s2 summed over a thread's rows in ascending order, shfl_xor
+// CPR..32, waves summed in index order.  One 128-row tile per block, plain grid, no inter-block
+// communication.
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -29,97 +29,41 @@
 #include "common.h"
 #include "kernels.h"
 #include "mfma.h"
+#include "tail_tile.h"
 
 namespace dpt {
 
 namespace tc3 {
-constexpr int BM = 128;
-constexpr int BK = 64;
-constexpr int kThreads = 256;
-constexpr int kRowBytes = BK * 2;
-constexpr int A_BYTES = BM * kRowBytes;
-constexpr uint32_t kOOB = 0xFFFFFF00u;  // past every descriptor's range: the load returns zeros
-
-__device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
+using namespace tail;
 
 // K-loop image (A tile, B tile, coefficients) and the epilogue image share the front of the LDS
 template <int BN>
 __host__ __device__ constexpr int lds_bytes(int C4, bool two) {
-  const int main = A_BYTES + BN * kRowBytes + (two ? 8 : 4) * C4 * 4, epi = BM * (BN * 2 + 16);
+  const int main = tile_bytes(BN) + (two ? 8 : 4) * C4 * 4, epi = image_bytes(BN);
   return main > epi ? main : epi;
 }
 }  // namespace tc3
 
-struct TailConv3BwdArgs {
-  const uint16_t* dz = nullptr;    // [M, C4] the tail's masked output gradient
-  const uint16_t* x3 = nullptr;    // [M, C4] the tail BatchNorm's input
-  const uint16_t* x2 = nullptr;    // [M, C4] the downsample BatchNorm's input (TWO)
-  const float* k = nullptr;        // [k1 | k2 | k3], 3 * C4 (the finalize's kbuf)
-  const float* mean = nullptr;     // [C4]
-  const float* j = nullptr;        // [j1 | j2 | j3] (TWO)
-  const float* mean2 = nullptr;    // [C4] (TWO)
-  const uint16_t* wt = nullptr;    // [C][C4] conv3's flipped weight
-  uint16_t* dx3 = nullptr;         // [M, C4]
-  uint16_t* dx_ds = nullptr;       // [M, C4] (TWO)
-  const uint16_t* bnx = nullptr;   // [M, C] bn2's input
-  const float* bn_mean = nullptr;  // [C]
-  const float* bn_coef = nullptr;  // [a | b], 2 * C
-  uint16_t* dx = nullptr;          // [M, C] conv3's input gradient
-  float* bp1 = nullptr;            // [C][m_tiles]
-  float* bp2 = nullptr;
-  int64_t M = 0;
-  int C4 = 0, m_tiles = 0, rev = 0;
-};
-
-// the conversions of IO::load8 / IO::store8, an element at a time
-template <typename IO>
-struct Cvt16;
-template <>
-struct Cvt16<BF16> {
-  __device__ static float up(uint32_t h) { return bf16_to_f32((uint16_t)h); }
-  __device__ static uint32_t down(float v) { return f32_to_bf16(v); }
-};
-template <>
-struct Cvt16<F16> {
-  __device__ static float up(uint32_t h) { return f16_to_f32((uint16_t)h); }
-  __device__ static uint32_t down(float v) { return F16::to16(v); }
-};
-
 template <typename IO, int BN, bool TWO>
-__global__ __launch_bounds__(tc3::kThreads, 2) void tail_conv3_bwd_kernel(TailConv3BwdArgs p) {
+__global__ __launch_bounds__(tail::kThreads, 2) void tail_conv3_bwd_kernel(TailConv3BwdArgs p) {
   using namespace tc3;
   constexpr bool F16V = std::is_same<IO, F16>::value;
-  constexpr int WN = BN / 64, WM = 4 / WN, MI = BM / (WM * 32), NI = 2;
-  constexpr int B_PER_T = BN * 8 / kThreads;  // weight chunks per thread and K-step
-  constexpr int C_STRIDE = BN * 2 + 16;
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  using T = Tile<F16V, BN>;
+  constexpr int B_PER_T = T::B_PER_T, C_STRIDE = T::C_STRIDE;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  unsigned char* la = lds;
-  unsigned char* lb = lds + A_BYTES;
-  float* lc = reinterpret_cast<float*>(lds + A_BYTES + BN * kRowBytes);  // [k1 | k2 | k3 | mean | j1 | j2 | j3 | mean2][C4]
+  float* lc = reinterpret_cast<float*>(lds + tile_bytes(BN));  // [k1 | k2 | k3 | mean | j1 | j2 | j3 | mean2][C4]
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid / WN, wn = wid % WN;
-  const int lr = lane & 31, lh = lane >> 5;
-  const int mt = p.rev ? p.m_tiles - 1 - (int)blockIdx.x : (int)blockIdx.x;
-  const int64_t m0 = (int64_t)mt * BM;
   const int C4 = p.C4, nk = C4 / BK;
+  const Rows t(p.M, C4, p.m_tiles, p.rev);
+  const int mt = t.mt, c = t.c, rb = t.rb;
+  const int64_t m0 = t.m0;
 
-  // this thread's chunks: column c (8 channels) of rows rb, rb + 32, rb + 64, rb + 96
-  const int c = tid & 7, rb = tid >> 3;
   const uint32_t nbytes = (uint32_t)(p.M * C4 * 2);
   const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)p.dz, 0, (int)nbytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x3, 0, (int)nbytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t r2 =
       __builtin_amdgcn_make_buffer_rsrc((void*)(TWO ? p.x2 : p.x3), 0, (int)nbytes, 0x00020000);
-  uint32_t voff[4];
-  bool live[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int64_t m = m0 + rb + 32 * i;
-    live[i] = m < p.M;
-    voff[i] = live[i] ? (uint32_t)((m * C4 + c * 8) * 2) : kOOB;
-  }
   // dx3 and dx_ds have dz's layout: the loads' byte offsets serve the stores; the weight rows go
   // through a descriptor too (32-bit offsets: no 64-bit address per row and chunk kept in VGPRs)
   const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)p.dx3, 0, (int)nbytes, 0x00020000);
@@ -131,10 +75,9 @@ __global__ __launch_bounds__(tc3::kThreads, 2) void tail_conv3_bwd_kernel(TailCo
 
   u32x4 ga[4], xa[4], qa[4];
   u32x4 wb[B_PER_T];
-  auto aoff = [&](int i, int ks) { return live[i] ? voff[i] + (uint32_t)ks * kRowBytes : kOOB; };
-  auto load_g = [&](int i, int ks) { ga[i] = __builtin_amdgcn_raw_buffer_load_b128(rg, aoff(i, ks), 0, 0); };
-  auto load_x = [&](int i, int ks) { xa[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, aoff(i, ks), 0, 0); };
-  auto load_q = [&](int i, int ks) { qa[i] = __builtin_amdgcn_raw_buffer_load_b128(r2, aoff(i, ks), 0, 0); };
+  auto load_g = [&](int i, int ks) { ga[i] = __builtin_amdgcn_raw_buffer_load_b128(rg, t.off(i, ks), 0, 0); };
+  auto load_x = [&](int i, int ks) { xa[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, t.off(i, ks), 0, 0); };
+  auto load_q = [&](int i, int ks) { qa[i] = __builtin_amdgcn_raw_buffer_load_b128(r2, t.off(i, ks), 0, 0); };
   auto load_a = [&](int i, int ks) {
     load_g(i, ks);
     load_x(i, ks);
@@ -144,11 +87,6 @@ __global__ __launch_bounds__(tc3::kThreads, 2) void tail_conv3_bwd_kernel(TailCo
 #pragma unroll
     for (int i = 0; i < B_PER_T; ++i)
       wb[i] = __builtin_amdgcn_raw_buffer_load_b128(rw, woff + (uint32_t)(i * 64 * C4), ks * kRowBytes, 0);
-  };
-  auto unpack = [&](const u32x4& w, float f[8]) {
-    const uint32_t u[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) f[k] = Cvt16<IO>::up(k & 1 ? u[k >> 1] >> 16 : u[k >> 1] & 0xffffu);
   };
 #pragma unroll
   for (int i = 0; i < 4; ++i) load_a(i, 0);
@@ -162,13 +100,8 @@ __global__ __launch_bounds__(tc3::kThreads, 2) void tail_conv3_bwd_kernel(TailCo
     if (TWO) lc[7 * C4 + i] = p.mean2[i];
   }
 
-  f32x16_t acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  typename T::Acc acc;
+  T::zero(acc);
 
   __syncthreads();  // the coefficients are staged
   for (int ks = 0; ks < nk; ++ks) {
@@ -178,8 +111,8 @@ __global__ __launch_bounds__(tc3::kThreads, 2) void tail_conv3_bwd_kernel(TailCo
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       float g[8], v[8];
-      unpack(ga[i], g);
-      unpack(xa[i], v);
+      unpack8<IO>(ga[i], g);
+      unpack8<IO>(xa[i], v);
       // the registers are free again: the next K-step's chunks are in flight from here, while the
       // rest of this K-step is applied, staged and multiplied
       if (more) load_x(i, ks + 1);
@@ -189,23 +122,14 @@ __global__ __launch_bounds__(tc3::kThreads, 2) void tail_conv3_bwd_kernel(TailCo
       for (int k = 0; k < 8; ++k) {
         // the expression of bn_bwd_apply_kernel / bn_bwd_apply2_kernel (bn_io.h)
         const float k1 = lc[ch0 + k], k2 = lc[C4 + ch0 + k], k3 = lc[2 * C4 + ch0 + k], mu = lc[3 * C4 + ch0 + k];
-        h[k] = Cvt16<IO>::down(bn_bwd_dx(k1, g[k], k2, v[k], mu, k3));
+        h[k] = down16<IO>(bn_bwd_dx(k1, g[k], k2, v[k], mu, k3));
       }
-      dv[i] = u32x4{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
-      if (live[i]) __builtin_amdgcn_raw_buffer_store_b128(dv[i], rd, voff[i], ks * kRowBytes, 0);
+      dv[i] = pack8(h);
+      if (t.live[i]) __builtin_amdgcn_raw_buffer_store_b128(dv[i], rd, t.voff[i], ks * kRowBytes, 0);
       else dv[i] = u32x4{0u, 0u, 0u, 0u};  // rows past M are zero rows of the GEMM
     }
     if (ks > 0) __syncthreads();  // every wave has multiplied the previous K-step
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = rb + 32 * i;
-      *reinterpret_cast<u32x4*>(la + row * kRowBytes + swz(row, c) * 16) = dv[i];
-    }
-#pragma unroll
-    for (int i = 0; i < B_PER_T; ++i) {
-      const int row = rb + 32 * i;
-      *reinterpret_cast<u32x4*>(lb + row * kRowBytes + swz(row, c) * 16) = wb[i];
-    }
+    T::stage(lds, dv, wb);
     if constexpr (TWO) {
       // the downsample branch's gradient (the second expression of bn_bwd_apply2_kernel) feeds no GEMM
       // here; a pass of its own after the A and B tiles are staged (their registers are free) that the
@@ -215,8 +139,8 @@ __global__ __launch_bounds__(tc3::kThreads, 2) void tail_conv3_bwd_kernel(TailCo
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float g[8], q[8];
-        unpack(ga[i], g);
-        unpack(qa[i], q);
+        unpack8<IO>(ga[i], g);
+        unpack8<IO>(qa[i], q);
         if (more) load_g(i, ks + 1);
         if (more) load_q(i, ks + 1);
         uint32_t h2[8];
@@ -224,57 +148,22 @@ __global__ __launch_bounds__(tc3::kThreads, 2) void tail_conv3_bwd_kernel(TailCo
         for (int k = 0; k < 8; ++k) {
           const float j1 = lc[4 * C4 + ch0 + k], j2 = lc[5 * C4 + ch0 + k], j3 = lc[6 * C4 + ch0 + k],
                       mu2 = lc[7 * C4 + ch0 + k];
-          h2[k] = Cvt16<IO>::down(bn_bwd_dx(j1, g[k], j2, q[k], mu2, j3));
+          h2[k] = down16<IO>(bn_bwd_dx(j1, g[k], j2, q[k], mu2, j3));
         }
-        if (live[i])
-          __builtin_amdgcn_raw_buffer_store_b128(
-              u32x4{h2[0] | (h2[1] << 16), h2[2] | (h2[3] << 16), h2[4] | (h2[5] << 16), h2[6] | (h2[7] << 16)}, re,
-              voff[i], ks * kRowBytes, 0);
+        if (t.live[i]) __builtin_amdgcn_raw_buffer_store_b128(pack8(h2), re, t.voff[i], ks * kRowBytes, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
     if (more) load_b(ks + 1);
     __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < BK / 16; ++kk) {
-      const int ch = kk * 2 + lh;
-      bf16x8_t fa[MI], fb[NI];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int row = wm * (MI * 32) + i * 32 + lr;
-        fa[i] = *reinterpret_cast<const bf16x8_t*>(la + row * kRowBytes + swz(row, ch) * 16);
-      }
-#pragma unroll
-      for (int j = 0; j < NI; ++j) {
-        const int row = wn * 64 + j * 32 + lr;
-        fb[j] = *reinterpret_cast<const bf16x8_t*>(lb + row * kRowBytes + swz(row, ch) * 16);
-      }
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j) acc[i][j] = cmfma<F16V>(fa[i], fb[j], acc[i][j]);
-    }
+    T::mma(lds, acc);
   }
   __syncthreads();  // the epilogue reuses the LDS
 
-  // ---- epilogue of conv_fwd_kernel (LDS image, BNB), operation for operation ----
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-      const int col = wn * 64 + j * 32 + lr;
-      const int rbase = wm * (MI * 32) + i * 32 + 4 * lh;
-#pragma unroll
-      for (int e = 0; e < 16; e += 2) {
-        const int r0 = rbase + (e & 3) + 8 * (e >> 2);
-        const f32x2_t v = {acc[i][j][e], acc[i][j][e + 1]};
-        const uint32_t u = cpack<F16V>(v);
-        *reinterpret_cast<uint16_t*>(lds + r0 * C_STRIDE + col * 2) = (uint16_t)u;
-        *reinterpret_cast<uint16_t*>(lds + (r0 + 1) * C_STRIDE + col * 2) = (uint16_t)(u >> 16);
-      }
-    }
+  // ---- the LDS image of tail_tile.h with the BNB sums of conv_fwd_kernel's epilogue ----
+  T::image(lds, acc, [](int, uint32_t) {});
   __syncthreads();
-  constexpr int CPR = BN / 8, RPP = kThreads / CPR, NPASS = BM / RPP, GRP = 4;
+  constexpr int CPR = T::CPR, RPP = T::RPP, NPASS = T::NPASS, GRP = 4;
   static_assert(NPASS % GRP == 0, "whole groups of passes");
   const int oc = tid % CPR, orow = tid / CPR;
   float ba[8], bb[8], bm[8], s1[8], s2[8];
@@ -357,44 +246,27 @@ static size_t tail_conv3_lds(int C4, int C, bool two) {
 }
 
 const char* tail_conv3_bwd_refusal(int64_t M, int64_t C4, int64_t C) {
-  if (C4 < 64 || C4 % 64 != 0) return "needs 4C % 64 == 0 and 4C >= 64";
-  if (C != 64 && C != 128) return "needs C of 64 or 128 (one output-channel tile)";
-  if (M < 1) return "empty input";
-  // 32-bit byte offsets through buffer descriptors, as conv_fwd_kernel (conv_check_offsets)
-  if (M * C4 * 2 >= 0xFFFFFF00ll || C * C4 * 2 >= 0x7FFFFFFFll) return "operand tensors beyond 2^31 elements";
+  if (const char* why = tail_tile_refusal(M, C4, C, "needs 4C % 64 == 0 and 4C >= 64",
+                                          "needs C of 64 or 128 (one output-channel tile)"))
+    return why;
   if (tail_conv3_lds((int)C4, (int)C, true) > 65536) return "the coefficients do not fit the LDS";
   // only where the unfused backward-data runs the tile this kernel reproduces
   return conv_dgrad_bnb_plain_tile_refusal(M, (int)C, C4);
 }
 
-template <typename IO>
-static void tail_conv3_dispatch(const TailConv3BwdArgs& a, int C, bool two, hipStream_t s) {
-  const dim3 grid((unsigned)a.m_tiles), block(tc3::kThreads);
+void launch_tail_conv3_bwd(bool f16, TailConv3BwdArgs a, int C, hipStream_t s) {
+  if (const char* why = tail_conv3_bwd_refusal(a.M, a.C4, C)) throw std::runtime_error(std::string("tail_conv3_bwd: ") + why);
+  const bool two = a.x2 != nullptr;
+  if (two && (a.mean2 == nullptr || a.dx_ds == nullptr)) throw std::runtime_error("tail_conv3_bwd: x2 needs mean2 and dx_ds");
+  a.j = two ? a.k + 3 * (int64_t)a.C4 : nullptr;
+  a.m_tiles = conv_m_tiles(a.M);
+  a.rev = kTailReverse;
+  const dim3 grid((unsigned)a.m_tiles), block(tail::kThreads);
   const size_t lds = tail_conv3_lds(a.C4, C, two);
-#define DPT_TC3(BN, TWOV) \
-  hipLaunchKernelGGL((tail_conv3_bwd_kernel<IO, BN, TWOV>), grid, block, lds, s, a)
-  if (C == 128) { if (two) DPT_TC3(128, true); else DPT_TC3(128, false); }
-  else { if (two) DPT_TC3(64, true); else DPT_TC3(64, false); }
-#undef DPT_TC3
-}
-
-// Apply passes walk the rows last-to-first (bn_kernels.hip kBnReverse): the rows the producing
-// backward-data wrote last are still in the caches.  The fused kernel takes its M-tiles in the same order.
-constexpr int kTail3Reverse = 1;
-
-void launch_tail_conv3_bwd(bool f16, const uint16_t* dz, const uint16_t* x3, const uint16_t* x2, const float* kbuf,
-                           const float* mean, const float* mean2, const uint16_t* wt, uint16_t* dx3, uint16_t* dx_ds,
-                           const uint16_t* bnx, const float* bn_mean, const float* bn_coef, uint16_t* dx, float* bp1,
-                           float* bp2, int64_t M, int C4, int C, hipStream_t s) {
-  if (const char* why = tail_conv3_bwd_refusal(M, C4, C)) throw std::runtime_error(std::string("tail_conv3_bwd: ") + why);
-  const bool two = x2 != nullptr;
-  if (two && (mean2 == nullptr || dx_ds == nullptr)) throw std::runtime_error("tail_conv3_bwd: x2 needs mean2 and dx_ds");
-  TailConv3BwdArgs a;
-  a.dz = dz; a.x3 = x3; a.x2 = x2; a.k = kbuf; a.mean = mean; a.j = two ? kbuf + 3 * (int64_t)C4 : nullptr;
-  a.mean2 = mean2; a.wt = wt; a.dx3 = dx3; a.dx_ds = dx_ds; a.bnx = bnx; a.bn_mean = bn_mean; a.bn_coef = bn_coef;
-  a.dx = dx; a.bp1 = bp1; a.bp2 = bp2; a.M = M; a.C4 = C4; a.m_tiles = conv_m_tiles(M); a.rev = kTail3Reverse;
-  if (f16) tail_conv3_dispatch<F16>(a, C, two, s);
-  else tail_conv3_dispatch<BF16>(a, C, two, s);
+  tail_dispatch(f16, C == 128, two, [&](auto h, auto w, auto t) {
+    hipLaunchKernelGGL((tail_conv3_bwd_kernel<std::conditional_t<h.value, F16, BF16>, w.value ? 128 : 64, t.value>), grid,
+                       block, lds, s, a);
+  });
 }
 
 }  // namespace dpt
