@@ -25,7 +25,9 @@ import os
 
 from . import native, native_available
 from . import conv as _conv
-from .conv import COMPACT_RES, MASKED_NO_RES, materialize_tail, take_bnb_partials
+from .conv import materialize_tail
+from .handover import (COMPACT_RES, MASKED_NO_RES, BnSource, TailLinks, TailPending, TailSlot,
+                       take_bnb_partials)
 
 # Block-tail BN+add+ReLU backward statistics in the consuming conv's dgrad epilogue (see _bwd)
 BNR_FUSE = os.environ.get("DPT_BNR_FUSE", "1") != "0"
@@ -82,10 +84,9 @@ class _BNActTrainPair(torch.autograd.Function):
 
 
 def _fwd(ctx, x, residual, weight, bias, running_mean, running_var, num_batches, momentum, eps, relu,
-         pair=False, partials=None, links=(None, None)):
+         pair=False, partials=None, links=TailLinks()):
     ps, pq = partials if partials is not None else (None, None)
-    own_slot, res_slot = links[0], links[1]
-    defer = links[2] if len(links) > 2 else None
+    own_slot, res_slot, defer = links.own_slot, links.res_slot, links.defer
     # block tail whose output feeds a native conv: the 1-bit ReLU mask that conv's dgrad epilogue
     # reads instead of y (1/16 of y's bytes; ops/conv.py BNR)
     mask = _relu_mask(x) if (own_slot is not None and relu and residual is not None) else None
@@ -96,7 +97,7 @@ def _fwd(ctx, x, residual, weight, bias, running_mean, running_var, num_batches,
                                                       num_batches, float(momentum), float(eps), bool(relu), ps, pq,
                                                       False)
         y = torch.empty_like(x)
-        defer.update(x3=x, r=residual, coef=coef, coef2=None, y=y, mask=mask)
+        defer.fill(x3=x, r=residual, coef=coef, coef2=None, y=y, mask=mask)
     else:
         y, mean, invstd, coef = native().bn_fwd_train(x, residual, weight, bias, running_mean, running_var,
                                                       num_batches, float(momentum), float(eps), bool(relu), ps, pq,
@@ -108,16 +109,16 @@ def _fwd(ctx, x, residual, weight, bias, running_mean, running_var, num_batches,
                           coef if mask_from_x else None)
     if mask_from_x:
         # a native conv consuming y sums this BN's backward statistics in its dgrad epilogue
-        y._dpt_bn_src = (x, mean, coef)
+        y._dpt_bn_src = BnSource(x, mean, coef)
     ctx.res_slot = res_slot  # our residual input is the identity alias of an earlier block tail
     # x came from a conv whose backward-data this tail's backward can run (ops/conv.py TAIL_CONV3_BWD_FUSE)
-    ctx.tail_link = links[3] if len(links) > 3 else None
+    ctx.tail_link = links.conv3
     if own_slot is not None:
         if mask is not None:
-            own_slot["mask"] = mask
+            own_slot.mask = mask
         # block tail: the conv consuming y sums the statistics (and folds in the identity-path
         # gradient the next block's tail leaves in own_slot, see _bwd) in its dgrad epilogue
-        y._dpt_bn_src = (x, mean, own_slot)
+        y._dpt_bn_src = BnSource(x, mean, slot=own_slot)
     return y
 
 
@@ -142,41 +143,32 @@ def _bwd(ctx, dy, dy2):
     if coef is not None and dy2 is None:
         part = take_bnb_partials(dy)
         if part is not None:  # statistics already summed by the consuming conv's dgrad epilogue
-            dx, dg, db = native().bn_bwd_partials(dy, x, weight, mean, invstd, coef, part[0], part[1],
+            dx, dg, db = native().bn_bwd_partials(dy, x, weight, mean, invstd, coef, part.p1, part.p2,
                                                   bool(want_params))
             return (dx, None, dg if want_params else None, db if want_params else None)
-    if dy2 is not None and ctx.relu and ctx.has_res:
+    if ctx.relu and ctx.has_res:
         part = take_bnb_partials(dy)
-        if part is not None and part[3] is not None:
+        if dy2 is not None and part is not None and part.p3 is not None:
             raise RuntimeError("fused block-tail backward: unexpected downsample statistic")
-        if part is not None:
-            # the consuming conv's dgrad epilogue already formed dz = (dy + dy2) * (y > 0) in dy's
-            # storage and summed its statistics (ops/conv.py); dz is also the residual gradient
-            if part[2] != dy2.data_ptr():
+        # dy2 delivered: the consuming conv's dgrad epilogue already formed dz = (dy + dy2) * (y > 0)
+        # in dy's storage and summed its statistics (ops/conv.py).  No dy2: the last block tail, where
+        # the average-pool backward formed dz = dy * (y > 0) (ops/pool.py gap_bwd_bnr), or COMPACT_RES,
+        # where the identity alias fed a 1x1 / stride-2 downsample conv, which handed its compact input
+        # gradient to the conv-path consumer and returned None to autograd (ops/conv.py
+        # S2_COMPACT_DRES): dy is the whole masked gradient, nothing is missing
+        if part is not None and (dy2 is not None or part.dres_ptr in (MASKED_NO_RES, COMPACT_RES)):
+            if dy2 is not None and part.dres_ptr != dy2.data_ptr():
                 raise RuntimeError("fused block-tail backward: the identity-path gradient folded into the "
                                    "conv's dgrad is not the one autograd delivered (alias used twice?)")
-            dx, dg, db = _apply_from_dz(ctx.tail_link, dy, x, weight, mean, invstd, part[0], part[1],
+            dx, dg, db = _apply_from_dz(ctx.tail_link, dy, x, weight, mean, invstd, part.p1, part.p2,
                                         bool(want_params))
             if ctx.res_slot is not None:
-                ctx.res_slot["dres"] = dy
-            return (dx, dy if want_dz else None, dg if want_params else None, db if want_params else None)
-    if dy2 is None and ctx.relu and ctx.has_res:
-        part = take_bnb_partials(dy)
-        if part is not None and part[2] in (MASKED_NO_RES, COMPACT_RES):
-            # the last block tail: the average-pool backward formed dz = dy * (y > 0) and summed
-            # the statistics (ops/pool.py gap_bwd_bnr); dz is also the residual gradient.
-            # COMPACT_RES: the identity alias fed a 1x1 / stride-2 downsample conv, which handed its
-            # compact input gradient to the conv-path consumer and returned None to autograd
-            # (ops/conv.py S2_COMPACT_DRES): dy is the whole masked gradient, nothing is missing
-            dx, dg, db = _apply_from_dz(ctx.tail_link, dy, x, weight, mean, invstd, part[0], part[1],
-                                        bool(want_params))
-            if ctx.res_slot is not None:
-                ctx.res_slot["dres"] = dy
+                ctx.res_slot.dres = dy   # dz is also the residual gradient
             return (dx, dy if want_dz else None, dg if want_params else None, db if want_params else None)
     dx, dg, db, dz = native().bn_bwd(_cl(dy), None if dy2 is None else _cl(dy2), y, x, weight, mean, invstd,
                                      ctx.relu, bool(want_dz), bool(want_params), coef)
     if want_dz and ctx.res_slot is not None:
-        ctx.res_slot["dres"] = dz  # picked up by the dgrad of the conv that consumed that alias
+        ctx.res_slot.dres = dz  # picked up by the dgrad of the conv that consumed that alias
     return (dx, dz if want_dz else None, dg if want_params else None, db if want_params else None)
 
 
@@ -206,15 +198,15 @@ class _BN2AddReLUPair(torch.autograd.Function):
         mask = _relu_mask(x) if own_slot is not None else None
         if defer is not None:  # TAIL_CONV1_FUSE: the consuming conv's forward fills y and the mask
             y = torch.empty_like(x)
-            defer.update(x3=x, r=x2, coef=coef, coef2=coef2, y=y, mask=mask)
+            defer.fill(x3=x, r=x2, coef=coef, coef2=coef2, y=y, mask=mask)
         else:
             y = C.bn_apply_aff(x, x2, coef, coef2, mask_out=mask)
         ctx.save_for_backward(x, x2, y, w, w2, mean, invstd, mean2, invstd2)
         ctx.tail_link = tail_link
         ctx.set_materialize_grads(False)
         if own_slot is not None:
-            own_slot["mask"] = mask
-            y._dpt_bn_src = (x, mean, own_slot, x2, mean2)
+            own_slot.mask = mask
+            y._dpt_bn_src = BnSource(x, mean, slot=own_slot, x2=x2, mean2=mean2)
         return y, y.view_as(y)
 
     @staticmethod
@@ -228,19 +220,19 @@ class _BN2AddReLUPair(torch.autograd.Function):
         want_params = any(want)
         C = native()
         part = take_bnb_partials(dy) if dy2 is not None else None
-        if part is not None and part[3] is not None:
-            if part[2] != dy2.data_ptr():
+        if part is not None and part.p3 is not None:
+            if part.dres_ptr != dy2.data_ptr():
                 raise RuntimeError("fused block-tail backward: the identity-path gradient folded into the "
                                    "conv's dgrad is not the one autograd delivered (alias used twice?)")
             if _conv.tail_bwd_refusal(ctx.tail_link, x) is None:
                 # the finalize only, then one kernel writes dx and dx2 and runs conv3's backward-data
                 # (ops/conv.py TAIL_CONV3_BWD_FUSE)
                 kbuf, _, dg, db, dg2, db2 = C.bn2_bwd_partials(dy, x, x2, w, w2, mean, invstd, mean2, invstd2,
-                                                               part[0], part[1], part[3], bool(want_params), False)
+                                                               part.p1, part.p2, part.p3, bool(want_params), False)
                 dx, dx2 = _conv.tail_bwd_apply(ctx.tail_link, dy, x, kbuf, mean, x2, mean2)
             else:
                 dx, dx2, dg, db, dg2, db2 = C.bn2_bwd_partials(dy, x, x2, w, w2, mean, invstd, mean2, invstd2,
-                                                               part[0], part[1], part[3], bool(want_params))
+                                                               part.p1, part.p2, part.p3, bool(want_params))
         else:
             if part is not None:
                 raise RuntimeError("fused block-tail backward: partials without the downsample statistic")
@@ -254,7 +246,7 @@ class _BN2AddReLUPair(torch.autograd.Function):
 
 
 def _tail_defer(x, own_slot, consumer):
-    """A fresh hand-over dict when the tail on ``x`` may leave its apply pass to ``consumer`` (the
+    """A fresh TailPending when the tail on ``x`` may leave its apply pass to ``consumer`` (the
     conv module that reads the tail's conv-path output, models/resnet.py), else None."""
     if not (TAIL_CONV1_FUSE and consumer is not None and own_slot is not None and torch.is_grad_enabled()):
         return None
@@ -264,7 +256,7 @@ def _tail_defer(x, own_slot, consumer):
     if getattr(consumer, "dpt_native_conv", True) is False:
         return None
     m = x.shape[0] * x.shape[2] * x.shape[3]
-    return {} if native().conv1x1_tail_refusal(m, x.shape[1], w.shape[0]) is None else None
+    return TailPending() if native().conv1x1_tail_refusal(m, x.shape[1], w.shape[0]) is None else None
 
 
 def run_tail_consumer(out, defer, consumer) -> None:
@@ -278,11 +270,11 @@ def run_tail_consumer(out, defer, consumer) -> None:
         consumer(yc)
     finally:
         yc.__dict__.pop("_dpt_tail_pending", None)
-        if not defer.get("done"):  # the call never reached the native conv: its result is void
+        if not defer.done:  # the call never reached the native conv: its result is void
             materialize_tail(defer)
-            defer.pop("conv", None)
-    if "conv" in defer:
-        yc._dpt_conv1_out = defer["conv"]
+            defer.conv = None
+    if defer.conv is not None:
+        yc._dpt_conv1_out = defer.conv
 
 
 def bn2_add_relu_train(x, bn, x2, bn2, consumer=None):
@@ -291,7 +283,7 @@ def bn2_add_relu_train(x, bn, x2, bn2, consumer=None):
     x2 = _cl(x2.to(x.dtype))
     partials = x.__dict__.pop("_dpt_bn_partials", None)
     partials2 = x2.__dict__.pop("_dpt_bn_partials", None)
-    own_slot = {} if (BNR_FUSE and x.dtype in (torch.bfloat16, torch.float16)) else None
+    own_slot = TailSlot() if (BNR_FUSE and x.dtype in (torch.bfloat16, torch.float16)) else None
     defer = _tail_defer(x, own_slot, consumer)
     out = _BN2AddReLUPair.apply(x, x2, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                 bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var, bn2.num_batches_tracked,
@@ -323,12 +315,12 @@ def bn_act_train(x: torch.Tensor, residual: Optional[torch.Tensor], weight, bias
     partials = x.__dict__.pop("_dpt_bn_partials", None)
     # block tails: own_slot receives the identity-path gradient from the next block's tail
     # backward (which runs before the backward of the conv consuming our conv-path output)
-    own_slot = {} if (pair and relu and residual is not None and BNR_FUSE
-                      and x.dtype in (torch.bfloat16, torch.float16)) else None
+    own_slot = TailSlot() if (pair and relu and residual is not None and BNR_FUSE
+                              and x.dtype in (torch.bfloat16, torch.float16)) else None
     fn = _BNActTrainPair if pair else _BNActTrain
     defer = _tail_defer(x, own_slot, consumer)
     out = fn.apply(x, residual, weight, bias, running_mean, running_var, num_batches, momentum, eps, relu,
-                   partials, (own_slot, res_slot, defer, x.__dict__.get("_dpt_tail_link")))
+                   partials, TailLinks(own_slot, res_slot, defer, x.__dict__.get("_dpt_tail_link")))
     if own_slot is not None:
         out[1]._dpt_res_slot = own_slot
     if defer is not None:

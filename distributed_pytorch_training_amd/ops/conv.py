@@ -23,6 +23,8 @@ import os
 import torch
 
 from . import native, native_available
+from .handover import (COMPACT_RES, MASKED_NO_RES, _BNB_PARTIALS, _GEN, _TAIL_STASHED,  # noqa: F401 (re-exported)
+                       Conv1Out, Conv3Link, _put_bnb, register_bnb_partials, reset_side_channels, take_bnb_partials)
 
 _CL = torch.channels_last
 # element types of the MFMA kernels (bf16 and fp16 operands, fp32 accumulation)
@@ -32,14 +34,6 @@ ENABLED = os.environ.get("DPT_NATIVE_CONV", "1") != "0"
 # Backward-data of a conv fed by a fused BN+ReLU also sums that BN's backward statistics in its
 # epilogue (the BN backward then skips its statistics pass).
 BN_BWD_FUSE = os.environ.get("DPT_BN_BWD_FUSE", "1") != "0"
-# dx.data_ptr() -> (generation, dx._version, p1, p2, shape, dres_ptr, p3): handed from a conv's
-# backward to the BN backward that receives dx as its output gradient (ops/bn.py), consumed once.
-# An entry is only honoured in the step generation that made it and while dx is unmodified (its
-# version counter unchanged: autograd accumulating a second gradient into dx in place would
-# invalidate the statistics); begin_step()/reset_side_channels() drop everything left over (an
-# aborted backward), so a reused allocation can never pick up stale statistics.
-_BNB_PARTIALS = {}
-_GEN = [0]
 # Stride-2 backward-data on the MFMA kernels (four parity-class convs); 0 = MIOpen
 S2_DGRAD = os.environ.get("DPT_S2_DGRAD", "1") != "0"
 # A 1x1 / stride-2 downsample conv fed by a block tail's identity alias hands its input gradient
@@ -121,14 +115,67 @@ def _note(kind, x, w, stride, pad, variant, e0, out_hw=(0, 0)):
     _CALLS.append((kind, key, variant, e0, _mark()))
 
 
+def _dgrad_stride1(ctx, dy, x, w, src, wt, red, stash, compact):
+    """(dx, variant) of a stride-1 conv; ``src``: the BnSource whose backward statistics the epilogue
+    sums, ``compact``: the tail's slot holds a downsample conv's compact gradient to fold."""
+    p = ctx.pad
+    if src is not None and not src.is_tail and stash is not None:
+        # the tail's backward formed dy and this gradient in one kernel
+        _put_bnb(stash.dx, stash.p1, stash.p2, None, None)
+        return stash.dx, "taken-from-tail"   # (the launch was noted as tail-bwd-apply+dgrad by the tail)
+    if src is not None and not src.is_tail:
+        dx, p1, p2, _ = native().conv_dgrad_bnstats(dy, w, p, src.x, src.mean, src.coef, w_flipped=wt,
+                                                    wgrad_reduce=red)
+        _put_bnb(dx, p1, p2, None, None)
+        return dx, "bnrelu-stats"
+    if (src is not None and _dres_ok(dres := src.slot.take_dres(), x)
+            and (compact or dres.shape == x.shape)):
+        # block-tail BN+add+ReLU (ops/bn.py pair outputs): the next block's tail already
+        # produced the identity-path gradient dres; dx becomes the tail's masked total
+        # gradient, the conv's input x is the tail's output y (the ReLU mask).  x2, mean2: the tail's
+        # identity path was a downsample BatchNorm folded into it (ops/bn.py _BN2AddReLUPair) - also
+        # sum that BN's statistic
+        x2, mean2 = src.x2, src.mean2
+        # the tail's 1-bit ReLU mask (ops/bn.py) is read instead of its output x when present
+        dx, p1, p2, p3 = native().conv_dgrad_bnstats(dy, w, p, src.x, src.mean, None, x, dres, wt, x2, mean2,
+                                                     wgrad_reduce=red, bn_mask=src.slot.mask,
+                                                     bn_res_s2=compact)
+        _put_bnb(dx, p1, p2, COMPACT_RES if compact else dres.data_ptr(), p3 if x2 is not None else None)
+        return dx, "tail-stats-s2res" if compact else "tail+ds-stats" if x2 is not None else "tail-stats"
+    dx = (native().conv_dgrad_flip(dy, w, p, wgrad_reduce=red)[0] if wt is None
+          else native().conv_dgrad_preflipped(dy, wt, p, wgrad_reduce=red))
+    return dx, "plain"
+
+
+def _dgrad_stride2(ctx, dy, x, w, red):
+    """(dx, variant) of a stride-2 conv on the parity-class kernels; dx is None when the gradient
+    went compact into the tail's slot (``s2-compact``)."""
+    p = ctx.pad
+    src = ctx.bn_src if BN_BWD_FUSE else None
+    rs = ctx.res_slot
+    if (ctx.compact_dres and S2_COMPACT_DRES and BN_BWD_FUSE and rs is not None and rs.fold_s2
+            and rs.dres is None):
+        # the conv-path consumer of the tail has not run yet and will fold (see conv2d)
+        rs.dres = native().conv_dgrad_s2(dy, w, p, x.shape[2], x.shape[3], wgrad_reduce=red, compact=True)[0]
+        rs.dres_s2 = True
+        return None, "s2-compact"
+    if src is not None and not src.is_tail and w.shape[2] > 1:
+        # BN+ReLU input: its backward statistics from the parity-class epilogues too
+        dx, p1, p2 = native().conv_dgrad_s2(dy, w, p, x.shape[2], x.shape[3], src.x, src.mean, src.coef,
+                                            wgrad_reduce=red)
+        _put_bnb(dx, p1, p2, None, None)
+        return dx, "s2-bnrelu-stats"
+    return native().conv_dgrad_s2(dy, w, p, x.shape[2], x.shape[3], wgrad_reduce=red)[0], "s2"
+
+
 def _backward(ctx, dy):
     x, w = ctx.saved_tensors
     dy = _cl(dy.to(x.dtype))
     s, p = ctx.stride, ctx.pad
-    dx = dw = red = None
+    dx = dw = red = variant = None
     # the tail that produced dy may already have run this conv's backward-data (TAIL_CONV3_BWD_FUSE)
     link = getattr(ctx, "tail_link", None)
-    stash = _take_tail_stash(link, dy, w) if (link is not None and TAIL_CONV3_BWD_FUSE) else None
+    stash = link.take_stash(dy, w) if (link is not None and TAIL_CONV3_BWD_FUSE) else None
     e0 = _mark()
     if ctx.needs_input_grad[1]:
         # (a taken stash: no backward-data launch will carry the reduce, so it is not deferred)
@@ -138,71 +185,24 @@ def _backward(ctx, dy):
             dw = native().conv_wgrad(dy, x, list(w.shape), s, p, False)
         _note("wgrad", x, w, s, p, "deferred-reduce" if red is not None else "reduce", e0)
         e0 = _mark()
-    variant = None
     if ctx.needs_input_grad[0]:
         src = ctx.bn_src if (s == 1 and BN_BWD_FUSE) else None
-        dres = None
         wt = _flipped(w) if s == 1 else None
-        slot = ctx.bn_src[2] if (ctx.bn_src is not None and isinstance(ctx.bn_src[2], dict)) else None
+        slot = ctx.bn_src.slot if ctx.bn_src is not None else None
         compact = False
         if slot is not None:
             # from here on the tail's downsample conv must not leave a compact gradient behind
-            slot.pop("fold_s2", None)
+            slot.fold_s2 = False
             # it ran first, left its compact gradient in the slot and returned None to autograd
             # (S2_COMPACT_DRES): fold it below, or nobody accounts for it
-            compact = bool(slot.pop("dres_s2", False))
-            if compact and not (src is not None and len(src) == 3 and _is_compact_of(slot.get("dres"), x)):
+            compact = slot.take_dres_s2()
+            if compact and not (src is not None and not src.has_downsample and _is_compact_of(slot.dres, x)):
                 raise RuntimeError("fused block-tail backward: a downsample conv handed over a compact "
                                    "identity-path gradient that this conv's backward-data cannot fold")
-        if src is not None and not isinstance(src[2], dict) and stash is not None:
-            # the tail's backward formed dy and this gradient in one kernel
-            dx, p1, p2 = stash
-            _put_bnb(dx, p1, p2, None, None)
-            variant = "taken-from-tail"   # (the launch was noted as tail-bwd-apply+dgrad by the tail)
-        elif src is not None and not isinstance(src[2], dict):  # BN+ReLU: (x, mean, coef)
-            bn_x, bn_mean, bn_coef = src
-            dx, p1, p2, _ = native().conv_dgrad_bnstats(dy, w, p, bn_x, bn_mean, bn_coef, w_flipped=wt,
-                                                        wgrad_reduce=red)
-            _put_bnb(dx, p1, p2, None, None)
-            variant = "bnrelu-stats"
-        elif (src is not None and _dres_ok(dres := src[2].pop("dres", None), x)   # (x, mean, slot)
-              and (compact or dres.shape == x.shape)):
-            # block-tail BN+add+ReLU (ops/bn.py pair outputs): the next block's tail already
-            # produced the identity-path gradient dres; dx becomes the tail's masked total
-            # gradient, the conv's input x is the tail's output y (the ReLU mask)
-            bn_x, bn_mean = src[0], src[1]
-            # (x, mean, slot, x2, mean2): the tail's identity path was a downsample BatchNorm
-            # folded into it (ops/bn.py _BN2AddReLUPair) - also sum that BN's statistic
-            x2, mean2 = (src[3], src[4]) if len(src) > 3 else (None, None)
-            # the tail's 1-bit ReLU mask (ops/bn.py) is read instead of its output x when present
-            dx, p1, p2, p3 = native().conv_dgrad_bnstats(dy, w, p, bn_x, bn_mean, None, x, dres, wt, x2, mean2,
-                                                         wgrad_reduce=red, bn_mask=src[2].get("mask"),
-                                                         bn_res_s2=compact)
-            _put_bnb(dx, p1, p2, COMPACT_RES if compact else dres.data_ptr(), p3 if x2 is not None else None)
-            variant = "tail-stats-s2res" if compact else "tail+ds-stats" if x2 is not None else "tail-stats"
-        elif s == 1:
-            dx = (native().conv_dgrad_flip(dy, w, p, wgrad_reduce=red)[0] if wt is None
-                  else native().conv_dgrad_preflipped(dy, wt, p, wgrad_reduce=red))
-            variant = "plain"
+        if s == 1:
+            dx, variant = _dgrad_stride1(ctx, dy, x, w, src, wt, red, stash, compact)
         elif s == 2 and S2_DGRAD and x.dim() == 4:
-            src = ctx.bn_src if BN_BWD_FUSE else None
-            rs = ctx.res_slot
-            if (ctx.compact_dres and S2_COMPACT_DRES and BN_BWD_FUSE and rs is not None and rs.get("fold_s2")
-                    and "dres" not in rs):
-                # the conv-path consumer of the tail has not run yet and will fold (see conv2d)
-                rs["dres"] = native().conv_dgrad_s2(dy, w, p, x.shape[2], x.shape[3], wgrad_reduce=red,
-                                                    compact=True)[0]
-                rs["dres_s2"] = True
-                variant = "s2-compact"
-            elif src is not None and not isinstance(src[2], dict) and w.shape[2] > 1:
-                # BN+ReLU input: its backward statistics from the parity-class epilogues too
-                dx, p1, p2 = native().conv_dgrad_s2(dy, w, p, x.shape[2], x.shape[3], src[0], src[1], src[2],
-                                                    wgrad_reduce=red)
-                _put_bnb(dx, p1, p2, None, None)
-                variant = "s2-bnrelu-stats"
-            else:
-                dx = native().conv_dgrad_s2(dy, w, p, x.shape[2], x.shape[3], wgrad_reduce=red)[0]
-                variant = "s2"
+            dx, variant = _dgrad_stride2(ctx, dy, x, w, red)
         else:
             dx = torch.ops.aten.convolution_backward(dy, x, w, None, (s, s), (p, p), (1, 1), False, (0, 0), 1,
                                                      (True, False, False))[0]
@@ -215,7 +215,7 @@ def _backward(ctx, dy):
     if dx is not None and ctx.res_slot is not None:
         # x is the identity alias of a fused block tail and this conv its downsample: hand the
         # identity-path gradient to the tail's conv-path consumer (see ops/bn.py)
-        ctx.res_slot["dres"] = dx
+        ctx.res_slot.dres = dx
     return dx, dw
 
 
@@ -224,19 +224,6 @@ def _backward(ctx, dy):
 # forward registers every such weight and the first backward-data of the step flips them all
 # in ONE launch (46 launches per ResNet-50 step otherwise).
 _FLIP = {"on": False, "pending": {}, "done": {}}
-
-
-def reset_side_channels() -> None:
-    """New step generation: forget every BN-backward hand-over not consumed so far."""
-    _GEN[0] += 1
-    _BNB_PARTIALS.clear()
-    for link in _TAIL_STASHED.values():
-        link.pop("stash", None)
-    _TAIL_STASHED.clear()
-
-
-def _put_bnb(dx, p1, p2, dres_ptr, p3) -> None:
-    _BNB_PARTIALS[dx.data_ptr()] = (_GEN[0], dx._version, p1, p2, tuple(dx.shape), dres_ptr, p3)
 
 
 def begin_step() -> None:
@@ -269,23 +256,22 @@ def _flipped(w: torch.Tensor):
 
 
 # ---- a block tail's backward apply fused with conv3's backward-data (TAIL_CONV3_BWD_FUSE) ----------
-# conv3's forward leaves a link dict {"w", "wv", "bn_src"} on its output x3 and on its own ctx.  The
+# conv3's forward leaves a Conv3Link (ops/handover.py) on its output x3 and on its own ctx.  The
 # tail's backward (ops/bn.py) finds it through x3, launches the fused kernel itself - it never returns
 # an unfilled dx3 - and stashes conv3's input gradient in the link; conv3's backward takes the stash
 # when the dy autograd hands it is that very dx3, unmodified, in the same step generation.
-_TAIL_STASHED = {}   # id -> link holding a stash (dropped by reset_side_channels)
 
 
 def _tail_link(x, w, stride, pad, out_hw, bn_src):
     """The link of an eligible conv3: native 1x1 / stride 1 / unpadded with statistics output whose
-    input comes from a fused BN+ReLU (``bn_src = (x, mean, coef)``), else None."""
+    input comes from a fused BN+ReLU (``bn_src.coef``), else None."""
     if not (TAIL_CONV3_BWD_FUSE and BN_BWD_FUSE and torch.is_grad_enabled() and x.requires_grad):
         return None
     if not (int(stride) == 1 and int(pad) == 0 and tuple(out_hw) == (0, 0) and w.shape[2] == 1 and w.shape[3] == 1):
         return None
-    if bn_src is None or len(bn_src) != 3 or isinstance(bn_src[2], dict):
+    if bn_src is None or bn_src.is_tail:
         return None
-    return {"w": w, "wv": w._version, "bn_src": bn_src}
+    return Conv3Link(w, w._version, bn_src)
 
 
 def tail_bwd_refusal(link, x3):
@@ -294,10 +280,10 @@ def tail_bwd_refusal(link, x3):
         return "switched off"
     if link is None:
         return "no link"
-    w = link["w"]
-    if w._version != link["wv"]:
+    w = link.w
+    if w._version != link.wv:
         return "the weight changed since the forward"
-    if x3.dtype not in _DT16 or w.dtype != x3.dtype or tuple(w.shape) != (x3.shape[1], link["bn_src"][0].shape[1], 1, 1):
+    if x3.dtype not in _DT16 or w.dtype != x3.dtype or tuple(w.shape) != (x3.shape[1], link.bn_src.x.shape[1], 1, 1):
         return "operand types or shapes"
     return native().conv1x1_tail_bwd_refusal(x3.numel() // x3.shape[1], x3.shape[1], w.shape[1])
 
@@ -315,38 +301,22 @@ def tail_bwd_apply(link, dz, x3, kbuf, mean, x2=None, mean2=None):
     c4 = x3.shape[1]
     dx3 = native().bn_bwd_apply_pre(dz, x3, mean, kbuf[:3 * c4])
     dx_ds = None if x2 is None else native().bn_bwd_apply_pre(dz, x2, mean2, kbuf[3 * c4:])
-    _note("dgrad", link["bn_src"][0], link["w"], 1, 0, "tail-bwd-refused", e0)
+    _note("dgrad", link.bn_src.x, link.w, 1, 0, "tail-bwd-refused", e0)
     return dx3, dx_ds
 
 
 def tail_bwd_launch(link, dz, x3, kbuf, mean, x2=None, mean2=None):
     """The fused launch for a tail whose finalize left ``kbuf``: (dx3, dx_ds | None), both filled;
     conv3's input gradient and bn2's statistics wait in the link for conv3's backward."""
-    w = link["w"]
+    w, src = link.w, link.bn_src
     wt = _flipped(w)
     if wt is None:   # no per-step flip cache (outside the trainer)
         wt = native().conv_wt_flip_multi([w])[0]
-    bn_x, bn_mean, bn_coef = link["bn_src"]
     e0 = _mark()
-    dx3, dx_ds, dx, p1, p2 = native().conv1x1_tail_bwd(dz, x3, x2, kbuf, mean, mean2, wt, bn_x, bn_mean, bn_coef)
-    link["stash"] = (dx3.data_ptr(), dx3._version, _GEN[0], tuple(dx3.shape), w._version, dx, p1, p2)
-    _TAIL_STASHED[id(link)] = link
-    _note("dgrad", bn_x, w, 1, 0, "tail-bwd-apply+dgrad", e0)
+    dx3, dx_ds, dx, p1, p2 = native().conv1x1_tail_bwd(dz, x3, x2, kbuf, mean, mean2, wt, src.x, src.mean, src.coef)
+    link.put_stash(dx3, dx, p1, p2)
+    _note("dgrad", src.x, w, 1, 0, "tail-bwd-apply+dgrad", e0)
     return dx3, dx_ds
-
-
-def _take_tail_stash(link, dy, w):
-    """(dx, p1, p2) the tail's backward left for the conv whose output gradient is ``dy``, once; None
-    when there is none or it was made for another tensor, version, step generation or weight."""
-    ent = link.pop("stash", None)
-    if ent is None:
-        return None
-    _TAIL_STASHED.pop(id(link), None)
-    ptr, ver, gen, shape, wv, dx, p1, p2 = ent
-    if (ptr != dy.data_ptr() or ver != dy._version or gen != _GEN[0] or shape != tuple(dy.shape)
-            or wv != w._version or link["w"].data_ptr() != w.data_ptr()):
-        return None
-    return dx, p1, p2
 
 
 def _is_compact_of(dres, x) -> bool:
@@ -382,31 +352,31 @@ class _Conv(torch.autograd.Function):
 def materialize_tail(pending) -> None:
     """Fill a block tail's deferred output ``y`` (and its ReLU mask) with the apply kernel the tail
     itself would have launched (ops/bn.py TAIL_CONV1_FUSE), once."""
-    if pending.get("done"):
+    if pending.done:
         return
-    x3, r, coef, coef2 = pending["x3"], pending["r"], pending["coef"], pending["coef2"]
+    x3, r, coef, coef2 = pending.x3, pending.r, pending.coef, pending.coef2
     c = x3.shape[1]
     if coef2 is None:
-        native().bn_apply(x3, r, coef[:c], coef[c:], True, mask_out=pending["mask"], y_out=pending["y"])
+        native().bn_apply(x3, r, coef[:c], coef[c:], True, mask_out=pending.mask, y_out=pending.y)
     else:
-        native().bn_apply_aff(x3, r, coef, coef2, mask_out=pending["mask"], y_out=pending["y"])
-    pending["done"] = True
+        native().bn_apply_aff(x3, r, coef, coef2, mask_out=pending.mask, y_out=pending.y)
+    pending.done = True
 
 
 def _tail_fwd(x, w, stride, pad, out_hw, pending):
     """The forward of a conv whose input ``x`` is a block tail's still unfilled output: one kernel
     writes ``x``, its mask and the conv output.  A conv the kernel refuses first materialises ``x``
     with the tail's own apply pass; None then, and the caller runs the plain forward."""
-    if pending["y"].data_ptr() != x.data_ptr() or tuple(out_hw) != (0, 0):
+    if pending.y.data_ptr() != x.data_ptr() or tuple(out_hw) != (0, 0):
         materialize_tail(pending)
         return None
     try:
-        out = native().conv1x1_tail_fwd(pending["x3"], pending["r"], pending["coef"], pending["coef2"], w, x,
-                                        pending["mask"], stride, pad)
+        out = native().conv1x1_tail_fwd(pending.x3, pending.r, pending.coef, pending.coef2, w, x,
+                                        pending.mask, stride, pad)
     except RuntimeError:
         materialize_tail(pending)
         return None
-    pending["done"] = True
+    pending.done = True
     return out
 
 
@@ -443,9 +413,9 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, bn_stats: bo
     # the tail that produced x already ran this very conv on it, fused with its apply pass
     # (ops/bn.py TAIL_CONV1_FUSE): hand that result over
     done = x.__dict__.pop("_dpt_conv1_out", None)
-    if done is not None and done[0] is w and done[1:4] == (int(stride), int(pad), bool(bn_stats)) \
-            and tuple(out_hw) == (0, 0):
-        return done[4]
+    if done is not None and done.w is w and (done.stride, done.pad, done.bn_stats) == (
+            int(stride), int(pad), bool(bn_stats)) and tuple(out_hw) == (0, 0):
+        return done.y
     # x is a block tail's output that is not filled yet: this conv's forward fills it
     pending = x.__dict__.pop("_dpt_tail_pending", None)
     if pending is not None and not bn_stats:
@@ -453,19 +423,19 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, bn_stats: bo
         pending = None
     if _FLIP["on"] and int(stride) == 1 and x.requires_grad:
         _FLIP["pending"].setdefault((w.data_ptr(), tuple(w.shape)), w)
-    # (BN input, mean, coef) of the fused BN+ReLU that produced x, if any (ops/bn.py)
+    # the fused BN+ReLU or block tail that produced x, if any (ops/bn.py)
     bn_src = x.__dict__.get("_dpt_bn_src")
     # x is the identity alias of a fused block tail (this conv is a downsample)
     res_slot = x.__dict__.get("_dpt_res_slot")
     one_by_one = w.shape[2] == 1 and w.shape[3] == 1
-    if (int(stride) == 1 and one_by_one and BN_BWD_FUSE and bn_src is not None and len(bn_src) == 3
-            and isinstance(bn_src[2], dict)):
+    if (int(stride) == 1 and one_by_one and BN_BWD_FUSE and bn_src is not None and bn_src.is_tail
+            and not bn_src.has_downsample):
         # a 1x1 / stride-1 conv on a block tail's conv-path output: its backward-data folds the
         # identity-path gradient (BNR), a stride-2 downsample conv's compact one included - told to
         # that conv (which runs after this one, models/resnet.py) through the shared slot
-        bn_src[2]["fold_s2"] = True
+        bn_src.slot.fold_s2 = True
     compact_dres = bool(S2_COMPACT_DRES and S2_DGRAD and int(stride) == 2 and one_by_one and int(pad) == 0
-                        and tuple(out_hw) == (0, 0) and res_slot is not None and res_slot.get("fold_s2"))
+                        and tuple(out_hw) == (0, 0) and res_slot is not None and res_slot.fold_s2)
     if not bn_stats:
         return _Conv.apply(x, w, int(stride), int(pad), tuple(out_hw), bn_src, res_slot, compact_dres)
     link = _tail_link(x, w, stride, pad, out_hw, bn_src)
@@ -475,39 +445,8 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, bn_stats: bo
     if link is not None:
         y._dpt_tail_link = link
     if pending is not None:  # fused or not, y is the result of this conv on the filled x
-        pending["conv"] = (w, int(stride), int(pad), True, y)
+        pending.conv = Conv1Out(w, int(stride), int(pad), True, y)
     return y
-
-
-# dres_ptr of an entry whose gradient is a block tail's already-masked gradient with no
-# identity-path gradient folded in (the last tail, whose output only fed the average pool)
-MASKED_NO_RES = -1
-# dres_ptr of an entry whose gradient is a block tail's masked gradient with a downsample conv's
-# compact identity-path gradient folded in (S2_COMPACT_DRES): autograd delivers no second gradient
-COMPACT_RES = -2
-
-
-def register_bnb_partials(dx: torch.Tensor, p1: torch.Tensor, p2: torch.Tensor, masked: bool = False) -> None:
-    """Hand BN backward-statistics partials summed by dx's producer to the BN backward that
-    receives dx as its output gradient (other producers than convs: the stem pool for BN+ReLU;
-    the average-pool backward for the last block tail, ``masked``: dx is already dz)."""
-    _put_bnb(dx, p1, p2, MASKED_NO_RES if masked else None, None)
-
-
-def take_bnb_partials(dy: torch.Tensor):
-    """(p1, p2, dres_ptr, p3) the backward of the conv that consumed a BN output summed for
-    ``dy``, once; dres_ptr is None for BN+ReLU, else the data pointer of the identity-path
-    gradient that was folded into ``dy`` (block tails); p3: the folded downsample BN's statistic
-    (tails with a downsample branch), else None."""
-    if not _BNB_PARTIALS:
-        return None
-    ent = _BNB_PARTIALS.pop(dy.data_ptr(), None)
-    if ent is None:
-        return None
-    gen, ver, p1, p2, shape, dres_ptr, p3 = ent
-    if gen != _GEN[0] or ver != dy._version or shape != tuple(dy.shape):
-        return None
-    return p1, p2, dres_ptr, p3
 
 
 def take_bn_partials(x: torch.Tensor):

@@ -10,6 +10,8 @@ from __future__ import annotations
 import torch
 
 from . import native, native_available
+from . import conv as _conv
+from .handover import register_bnb_partials
 
 
 class _MaxPoolNHWC(torch.autograd.Function):
@@ -41,7 +43,7 @@ class _MaxPoolNHWCPair(torch.autograd.Function):
         y, idx = native().maxpool_fwd(x, k, stride, pad)
         ctx.save_for_backward(idx)
         ctx.cfg = (x.shape[2], x.shape[3], k, stride, pad)
-        # (BN input, mean, coef) of the fused BN+ReLU that produced x (the ResNet stem): the
+        # the BnSource of the fused BN+ReLU that produced x (the ResNet stem): the
         # backward gather also sums that BN's backward statistics (ops/bn.py picks them up)
         ctx.bn_src = bn_src if (bn_src is not None and (k, stride, pad) == (3, 2, 1)) else None
         ctx.mark_non_differentiable(idx)
@@ -50,8 +52,6 @@ class _MaxPoolNHWCPair(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, dy2):
-        from .conv import BN_BWD_FUSE, register_bnb_partials
-
         (idx,) = ctx.saved_tensors
         H, W, k, s, p = ctx.cfg
         if dy is None:
@@ -61,9 +61,9 @@ class _MaxPoolNHWCPair(torch.autograd.Function):
         dy = _cl(dy)
         if dy2 is not None:
             dy2 = _cl(dy2.to(dy.dtype))
-        src = ctx.bn_src if BN_BWD_FUSE else None
-        if src is not None and src[0].dtype == dy.dtype:
-            dx, p1, p2 = native().maxpool_bwd(dy, idx, H, W, k, s, p, dy2, src[0], src[1], src[2])
+        src = ctx.bn_src if _conv.BN_BWD_FUSE else None
+        if src is not None and src.x.dtype == dy.dtype:
+            dx, p1, p2 = native().maxpool_bwd(dy, idx, H, W, k, s, p, dy2, src.x, src.mean, src.coef)
             register_bnb_partials(dx, p1, p2)
         else:
             dx = native().maxpool_bwd(dy, idx, H, W, k, s, p, dy2)[0]
@@ -99,14 +99,13 @@ class _GlobalAvgPoolNHWC(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         ctx.cfg = (x.shape[2], x.shape[3], x.dtype)
-        # x is the output of the network's last fused block tail (ops/bn.py: (BN input, mean,
-        # slot), no downsample BN folded in): the backward also forms that tail's masked
+        # x is the output of the network's last fused block tail (ops/bn.py: a BnSource with a
+        # slot, no downsample BN folded in): the backward also forms that tail's masked
         # gradient and sums its BN statistics (gap_bwd_bnr), as a conv's backward-data epilogue
         # does for every other tail - the BN backward then skips its statistics pass
         src = x.__dict__.get("_dpt_bn_src")
-        from .conv import BN_BWD_FUSE
         ctx.bn_src = None
-        if (BN_BWD_FUSE and src is not None and len(src) == 3 and isinstance(src[2], dict)
+        if (_conv.BN_BWD_FUSE and src is not None and src.is_tail and not src.has_downsample
                 and x.dtype in (torch.bfloat16, torch.float16) and 256 % (x.shape[1] // 8) == 0):
             ctx.bn_src = src
             ctx.save_for_backward(x)
@@ -117,9 +116,8 @@ class _GlobalAvgPoolNHWC(torch.autograd.Function):
         H, W, dt = ctx.cfg
         g2 = g.reshape(g.shape[0], g.shape[1]).contiguous()
         if ctx.bn_src is not None:
-            from .conv import register_bnb_partials
             (y,) = ctx.saved_tensors
-            dz, p1, p2 = native().gap_bwd_bnr(g2, y, ctx.bn_src[0], ctx.bn_src[1])
+            dz, p1, p2 = native().gap_bwd_bnr(g2, y, ctx.bn_src.x, ctx.bn_src.mean)
             register_bnb_partials(dz, p1, p2, masked=True)
             return dz
         return native().gap_bwd(g2, H, W, dt)

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from distributed_pytorch_training_amd.ops import conv as native_conv
+from distributed_pytorch_training_amd.ops.handover import BnSource, TailSlot
 
 CL = torch.channels_last
 
@@ -78,7 +79,7 @@ def _case(c=64, c4=256):
     bn_x = torch.randn(n, c, h, w_).to(torch.bfloat16).contiguous(memory_format=CL)
     x = torch.randn(n, c, h, w_).to(torch.bfloat16).contiguous(memory_format=CL).requires_grad_(True)
     w = torch.randn(c4, c, 1, 1).to(torch.bfloat16).contiguous(memory_format=CL).requires_grad_(True)
-    bn_src = (bn_x, torch.zeros(c), torch.zeros(2 * c))
+    bn_src = BnSource(bn_x, torch.zeros(c), torch.zeros(2 * c))
     x3 = torch.randn(n, c4, h, w_).to(torch.bfloat16).contiguous(memory_format=CL)
     dz = torch.randn_like(x3)
     link = native_conv._tail_link(x, w, 1, 0, (0, 0), bn_src)
@@ -94,14 +95,14 @@ def _tail(link, x3, dz):
 
 def test_link_only_for_an_eligible_conv3(fake):
     ctx, link, x3, dz, w = _case()
-    assert link is not None and link["w"] is w and link["wv"] == w._version and link["bn_src"] is ctx.bn_src
+    assert link is not None and link.w is w and link.wv == w._version and link.bn_src is ctx.bn_src
     x = ctx.saved_tensors[0].requires_grad_(True)
     w3 = torch.randn(256, 64, 3, 3).to(torch.bfloat16).contiguous(memory_format=CL)
     assert native_conv._tail_link(x, w3, 1, 1, (0, 0), ctx.bn_src) is None                  # 3x3
     assert native_conv._tail_link(x, w, 2, 0, (0, 0), ctx.bn_src) is None                   # stride 2
     assert native_conv._tail_link(x, w, 1, 0, (3, 3), ctx.bn_src) is None                   # explicit output size
     assert native_conv._tail_link(x, w, 1, 0, (0, 0), None) is None                         # no BN+ReLU before it
-    assert native_conv._tail_link(x, w, 1, 0, (0, 0), (ctx.bn_src[0], ctx.bn_src[1], {})) is None   # a block tail
+    assert native_conv._tail_link(x, w, 1, 0, (0, 0), BnSource(ctx.bn_src.x, ctx.bn_src.mean, slot=TailSlot())) is None   # a block tail
     assert native_conv._tail_link(x.detach(), w, 1, 0, (0, 0), ctx.bn_src) is None          # no input gradient
     with torch.no_grad():
         assert native_conv._tail_link(x, w, 1, 0, (0, 0), ctx.bn_src) is None
@@ -124,13 +125,13 @@ def test_refusals_reach_the_tail(fake, monkeypatch):
 def test_stash_is_taken_once(fake):
     ctx, link, x3, dz, w = _case()
     dx3 = _tail(link, x3, dz)
-    assert (dx3 == 3.0).all() and "stash" in link and len(native_conv._TAIL_STASHED) == 1
+    assert (dx3 == 3.0).all() and link.stash is not None and len(native_conv._TAIL_STASHED) == 1
     fake.calls.clear()
     dx, dw = native_conv._backward(ctx, dx3)
     assert (dx == 5.0).all() and fake.calls == ["wgrad+reduce"]              # no backward-data launch
-    assert "stash" not in link and not native_conv._TAIL_STASHED
+    assert link.stash is None and not native_conv._TAIL_STASHED
     part = native_conv.take_bnb_partials(dx)
-    assert part is not None and (part[0] == 1.0).all() and part[2] is None   # bn2's statistics travel on
+    assert part is not None and (part.p1 == 1.0).all() and part.dres_ptr is None   # bn2's statistics travel on
     fake.calls.clear()
     dx, dw = native_conv._backward(ctx, dx3)                                 # a second backward: nothing left
     assert (dx == 2.0).all() and fake.calls == ["wgrad", "dgrad"]
@@ -155,7 +156,7 @@ def test_stash_is_ignored_on_a_mismatch(fake, how):
         dy = fold(dx3)
         assert dy.data_ptr() == dx3.data_ptr() and dy._version == dx3._version and dy.shape != dx3.shape
         ctx.saved_tensors = (fold(ctx.saved_tensors[0]), w)
-        ctx.bn_src = tuple(fold(t) if t.dim() == 4 else t for t in ctx.bn_src)
+        ctx.bn_src = BnSource(fold(ctx.bn_src.x), ctx.bn_src.mean, ctx.bn_src.coef)
     elif how == "weight-version":
         with torch.no_grad():
             w.mul_(2.0)
@@ -164,17 +165,17 @@ def test_stash_is_ignored_on_a_mismatch(fake, how):
     fake.calls.clear()
     dx, dw = native_conv._backward(ctx, dy)
     assert (dx == 2.0).all() and fake.calls == ["wgrad", "dgrad"]            # the unfused backward-data
-    assert "stash" not in link and not native_conv._TAIL_STASHED             # and the stash is gone
+    assert link.stash is None and not native_conv._TAIL_STASHED             # and the stash is gone
 
 
 @pytest.mark.parametrize("drop", ["begin_step", "reset_side_channels"])
 def test_leftover_stash_is_dropped(fake, drop):
     ctx, link, x3, dz, w = _case()
     dx3 = _tail(link, x3, dz)
-    assert "stash" in link
+    assert link.stash is not None
     getattr(native_conv, drop)()
     native_conv.end_caching()
-    assert "stash" not in link and not native_conv._TAIL_STASHED
+    assert link.stash is None and not native_conv._TAIL_STASHED
     fake.calls.clear()
     dx, dw = native_conv._backward(ctx, dx3)
     assert (dx == 2.0).all() and fake.calls == ["wgrad", "dgrad"]
@@ -185,12 +186,11 @@ def test_stash_is_never_consulted_with_the_switch_off(fake, monkeypatch):
     dx3 = _tail(link, x3, dz)
     monkeypatch.setattr(native_conv, "TAIL_CONV3_BWD_FUSE", False)           # flipped before conv3's backward
 
-    class _NoTouch(dict):
-        def pop(self, *a):
+    class _NoTouch:
+        def __getattr__(self, name):
             raise AssertionError("the link was consulted")
 
-    guarded = _NoTouch(link)
-    ctx.tail_link = guarded
+    ctx.tail_link = _NoTouch()
     fake.calls.clear()
     dx, dw = native_conv._backward(ctx, dx3)
     assert (dx == 2.0).all() and fake.calls == ["wgrad", "dgrad"]
@@ -230,7 +230,7 @@ def test_a_launch_the_binding_refuses_falls_back_to_the_apply_pass(fake, two, mo
     monkeypatch.setattr(native_conv, "_CALLS", None)
     assert (dx3 == 7.0).all() and (dx_ds is None) == (not two)               # filled by the apply pass(es)
     assert fake.calls == ["flip", "fused"] + ["apply"] * (2 if two else 1)
-    assert "stash" not in link and not native_conv._TAIL_STASHED and noted == ["tail-bwd-refused"]
+    assert link.stash is None and not native_conv._TAIL_STASHED and noted == ["tail-bwd-refused"]
     fake.calls.clear()
     dx, dw = native_conv._backward(ctx, dx3)                                 # conv3 runs its own backward-data
     assert (dx == 2.0).all() and fake.calls == ["wgrad", "dgrad"]
