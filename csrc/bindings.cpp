@@ -456,7 +456,8 @@ static uint8_t* relu_mask_ptr(const c10::optional<Tensor>& m, int64_t M, int64_t
 // that produced the conv's input (bn_x: that BN's input, same shape as dx; coef = [a | b]).
 // Returns {dx, p1, p2} with p1/p2 [C, m_tiles] for bn_bwd_partials.
 // With bn_y / bn_res (block-tail BN+add+ReLU whose output also fed the identity path): dx is
-// the tail's whole masked gradient (dx + bn_res) * (bn_y > 0) and p1/p2 are summed from it.
+// the tail's whole masked gradient (dx + bn_res) * (bn_y > 0), an fp32 sum rounded to 16 bits for
+// the store; p1/p2 (and p3) are summed from the fp32 value before that rounding.
 std::vector<Tensor> conv_dgrad_bnstats(Tensor dy, Tensor w, int64_t pad, Tensor bn_x, Tensor bn_mean,
                                        c10::optional<Tensor> bn_coef,
                                        c10::optional<Tensor> bn_y, c10::optional<Tensor> bn_res,
@@ -1667,6 +1668,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_set_splitk", &dpt::conv_set_splitk, py::arg("mode"));
   m.def("conv_get_splitk", &dpt::conv_get_splitk);
   m.def("conv_set_fwd_shape_policy", &dpt::conv_set_fwd_shape_policy, py::arg("bits"));
+  m.def("conv_trace", &dpt::conv_trace, py::arg("on"),
+        "record one line per conv launch (kernel and template configuration) while on");
+  m.def("conv_trace_take", &dpt::conv_trace_take, "the calling thread's recorded launches; clears the list");
   m.def("conv_dgrad", &conv_dgrad, py::arg("grad_output"), py::arg("w"), py::arg("pad"));
   m.def("conv_dgrad_bnstats", &conv_dgrad_bnstats, py::arg("grad_output"), py::arg("w"), py::arg("pad"),
         py::arg("bn_x"), py::arg("bn_mean"), py::arg("bn_coef"), py::arg("bn_y") = py::none(),

@@ -30,7 +30,9 @@
 #include <cstdlib>
 #include <mutex>
 #include <stdexcept>
+#include <string>
 #include <type_traits>
+#include <vector>
 
 #include "carry.h"
 #include "gelu.h"
@@ -175,8 +177,10 @@ __device__ __attribute__((aligned(64))) uint4 g_conv_zero16[4];
 // BNR (with BNB): the BatchNorm was a residual-block tail y = relu(bn(x) + res) whose output
 // fed this conv AND the next block's identity path: the stored gradient is the block tail's
 // whole masked gradient dz = (g + g_identity) * (y > 0) - the tail's residual-path gradient
-// and the input of its backward apply - and s1/s2 are summed from it.  Replaces the
-// tail's backward-statistics pass (4 reads + 1 write of a 4C-channel tensor) by 3 reads here.
+// and the input of its backward apply.  g is the 16-bit rounded conv output; dz is the fp32 sum,
+// rounded once more for the store, and s1/s2 are summed from the fp32 dz BEFORE that second
+// rounding, exactly as bn_bwd_stats_kernel (the pass this replaces) sums the dz it stores.  Replaces
+// the tail's backward-statistics pass (4 reads + 1 write of a 4C-channel tensor) by 3 reads here.
 // REMAP (LDS epilogue): output rows scattered to one stride-2 parity class of a larger image
 // (strided backward-data); ZSIB: also write zeros to the other three positions of each 2x2
 // cell (1x1 / stride-2 backward-data, whose other classes receive no gradient).
@@ -1108,7 +1112,8 @@ __global__ __launch_bounds__(NT, (SK || BREG) ? 4 : 2) void conv_fwd_kernel(Conv
 // rows, so the slab is kept short to spread the split sums over many blocks.  Identical
 // per-element math to conv_fwd_kernel's LDS epilogue (16-bit rounding of the sum, BN
 // statistics from the rounded values; BNB: s1 = sum dz, s2 = sum dz*(x - mean) with the BN+ReLU
-// mask; BNR: dz = (g + res) * (y > 0) is what is stored; BNR2: s3 = sum dz*(x2 - mean2)).
+// mask; BNR: dz = (g + res) * (y > 0) in fp32 is what is summed, and what is stored after its
+// rounding to 16 bits; BNR2: s3 = sum dz*(x2 - mean2)).
 // Statistics partials: one column per 16-row slab, [C][ceil(M/16)] (conv_split_cols).
 constexpr int kSplitRows = 16;
 // RS2: the BNR residual is a stride-2 downsample conv's compact gradient (ConvFwdArgs::rHo).
@@ -2236,7 +2241,8 @@ void conv_set_splitk_policy(int tiles, int eager_tiles, int eager_min_k, int tar
 //   4 / 8: 1x1 stride-1 convs with the statistics epilogue on grids under 1,024 tiles (the deep
 //      reducing convs at 14x14 / 7x7, latency-bound with ~3 resident blocks per CU:
 //      profiles/step_pmc_r5.md) -> the BK = 32 pipelined K loop, 2 stages (variant 14, 4 blocks
-//      per CU) / 3 stages (variant 7).
+//      per CU) / 3 stages (variant 7).  As launched today both codes run the 256-row LDS-epilogue
+//      tile (conv_fwd_dispatch, see conv_set_variant above; tests/test_conv_exact_gpu.py pins it).
 static int g_fwd_shape_policy = 0;
 void conv_set_fwd_shape_policy(int bits) { g_fwd_shape_policy = bits; }
 
@@ -2280,8 +2286,36 @@ static constexpr unsigned opt(bool on, unsigned f) { return on ? f : 0u; }
 template <unsigned F>
 using Opts = std::integral_constant<unsigned, F>;
 
+// ---- launch trace (conv_trace / conv_trace_take, kernels.h) ------------------------------------------
+static bool g_trace_on = false;
+static thread_local std::vector<std::string> g_trace;
+void conv_trace(bool on) { g_trace_on = on; }
+std::vector<std::string> conv_trace_take() {
+  std::vector<std::string> out;
+  out.swap(g_trace);
+  return out;
+}
+// The flag word by name, in bit order: "kLdsEpi|kStats" ("0": no flag).
+static std::string flag_names(unsigned f) {
+  static const char* const kNames[] = {"kLdsEpi", "kBkn", "kStats", "kBnb", "kBnr", "kRemap", "kZsib", "kBnr2",
+                                       "kF16", "kSplit", "kHalo", "kSk", "kDgelu", "kBreg", "kDir", "kRs2"};
+  std::string out;
+  for (int b = 0; b < 16; ++b)
+    if (f & (1u << b)) out += (out.empty() ? "" : "|") + std::string(kNames[b]);
+  return out.empty() ? "0" : out;
+}
+static std::string grid_str(dim3 g) {
+  return "grid=" + std::to_string(g.x) + "x" + std::to_string(g.y);
+}
+
 template <int BMT, int BN, int STAGES, unsigned F, int NT = conv::kThreads, int HB = 1>
 static void launch_fwd_kernel(dim3 grid, hipStream_t s, const ConvFwdArgs& a) {
+  if (g_trace_on)
+    g_trace.push_back("fwd BM=" + std::to_string(BMT) + " BN=" + std::to_string(BN) + " STAGES=" +
+                      std::to_string(STAGES) + " F=" + flag_names(F) + " NT=" + std::to_string(NT) + " HB=" +
+                      std::to_string(HB) + " " + grid_str(grid) + " splits=" + std::to_string(a.splits) + " kps=" +
+                      std::to_string(a.kps) + " skG=" + std::to_string(a.sk.G) + " carry=" +
+                      std::to_string(a.red.blocks));
   hipLaunchKernelGGL((conv_fwd_kernel<BMT, BN, STAGES, has(F, kLdsEpi), has(F, kBkn), has(F, kStats), has(F, kBnb),
                                       has(F, kBnr), has(F, kRemap), has(F, kZsib), has(F, kBnr2), has(F, kF16), NT,
                                       has(F, kSplit), has(F, kHalo), HB, has(F, kSk), has(F, kDgelu), has(F, kBreg),
@@ -2291,6 +2325,8 @@ static void launch_fwd_kernel(dim3 grid, hipStream_t s, const ConvFwdArgs& a) {
 
 template <unsigned F>
 static void launch_split_epilogue_kernel(dim3 grid, hipStream_t s, const ConvFwdArgs& a) {
+  if (g_trace_on)
+    g_trace.push_back("split_epilogue F=" + flag_names(F) + " " + grid_str(grid) + " splits=" + std::to_string(a.splits));
   hipLaunchKernelGGL((conv_split_epilogue_kernel<has(F, kStats), has(F, kBnb), has(F, kBnr), has(F, kBnr2),
                                                  has(F, kRemap), has(F, kZsib), has(F, kF16), has(F, kRs2)>),
                      grid, dim3(256), 0, s, a);
@@ -2298,11 +2334,18 @@ static void launch_split_epilogue_kernel(dim3 grid, hipStream_t s, const ConvFwd
 
 template <int BMW, int BNW, int STAGES, unsigned F, int NT = conv::kThreads>
 static void launch_wgrad_kernel(dim3 grid, hipStream_t s, const ConvWgradArgs& a) {
+  if (g_trace_on)
+    g_trace.push_back("wgrad BMW=" + std::to_string(BMW) + " BNW=" + std::to_string(BNW) + " STAGES=" +
+                      std::to_string(STAGES) + " F=" + flag_names(F) + " NT=" + std::to_string(NT) + " " +
+                      grid_str(grid) + " splits=" + std::to_string(a.splits));
   hipLaunchKernelGGL((conv_wgrad_kernel<BMW, BNW, STAGES, has(F, kF16), NT, has(F, kDir)>), grid, dim3(NT), 0, s, a);
 }
 
 template <int BNW, int STAGES, unsigned F>
 static void launch_wgrad_halo_kernel(dim3 grid, hipStream_t s, const ConvWgradArgs& a) {
+  if (g_trace_on)
+    g_trace.push_back("wgrad_halo BNW=" + std::to_string(BNW) + " STAGES=" + std::to_string(STAGES) + " F=" +
+                      flag_names(F) + " " + grid_str(grid) + " splits=" + std::to_string(a.splits));
   hipLaunchKernelGGL((conv_wgrad_halo_kernel<BNW, STAGES, has(F, kF16)>), grid, dim3(conv::kThreads), 0, s, a);
 }
 
@@ -2345,6 +2388,9 @@ void launch_wgrad_reduce(const WgradReduce& r, hipStream_t st) {
   const float4* part = reinterpret_cast<const float4*>(r.part);
   const int ph = reduce_phases(r.splits), out_per_block = kBlock / ph;
   const dim3 grid((unsigned)((r.n4 + out_per_block - 1) / out_per_block)), block(kBlock);
+  if (g_trace_on)
+    g_trace.push_back("wgrad_reduce PH=" + std::to_string(ph) + " splits=" + std::to_string(r.splits) + " kind=" +
+                      std::to_string(r.kind) + " " + grid_str(grid));
   if (ph == 16) hipLaunchKernelGGL(conv_wgrad_reduce_kernel<16>, grid, block, 0, st, part, r.n4, r.splits, r.out, r.kind);
   else if (ph == 4) hipLaunchKernelGGL(conv_wgrad_reduce_kernel<4>, grid, block, 0, st, part, r.n4, r.splits, r.out, r.kind);
   else hipLaunchKernelGGL(conv_wgrad_reduce_kernel<1>, grid, block, 0, st, part, r.n4, r.splits, r.out, r.kind);
@@ -2376,6 +2422,9 @@ int take_attached_reduce(ReduceCarry& rc) {
   rc.kind = r->kind;
   rc.ph = reduce_phases(r->splits);
   rc.blocks = (int)((r->n4 + kBlock / rc.ph - 1) / (kBlock / rc.ph));
+  if (g_trace_on)
+    g_trace.push_back("carry_reduce PH=" + std::to_string(rc.ph) + " splits=" + std::to_string(rc.splits) + " kind=" +
+                      std::to_string(rc.kind) + " blocks=" + std::to_string(rc.blocks));
   return rc.blocks;
 }
 

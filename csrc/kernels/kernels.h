@@ -5,6 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+#include <vector>
+
 namespace dpt {
 
 struct AugNorm {
@@ -265,6 +268,12 @@ void conv_set_splitk_policy(int tiles, int eager_tiles, int eager_min_k, int tar
 void conv_set_splitk(int mode);  // 0 off / 1 auto (default, DPT_CONV_SPLITK) / 2 in-graph policy always
 int conv_get_splitk();
 void conv_set_fwd_shape_policy(int bits);  // per-shape forward tiles (conv_kernels.hip)
+// Launch trace (host only, tests): while on, every conv_fwd_kernel / split-epilogue / backward-weight /
+// reduce launch of conv_kernels.hip, and every reduce taken into another launch's grid, appends one
+// line naming the kernel and its template configuration to a per-thread list; conv_trace_take
+// returns and clears the calling thread's list.  Off (default): one branch per launch.
+void conv_trace(bool on);
+std::vector<std::string> conv_trace_take();
 void launch_conv_fwd(const uint16_t* x, const uint16_t* w, uint16_t* y, int N, int H, int W, int C, int Cout,
                      int R, int S, int stride, int pad, float* psum, float* psq, hipStream_t s, int Ho = 0,
                      int Wo = 0, bool f16 = false, float* ws = nullptr);
