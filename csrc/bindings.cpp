@@ -800,86 +800,97 @@ Tensor im2col(Tensor x, int64_t R, int64_t S, int64_t stride, int64_t pad, int64
 }
 
 // ---- fused self-attention (ViT) ---------------------------------------------------------------
-void check_bf16_contig(const Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.is_contiguous(), name,
-              " must be a contiguous bf16 GPU tensor");
+// One body per entry point for both element types: the bf16 and the _f16 bindings differ in the
+// dtype they require and the launcher they call, nothing else (same shape, contiguity, lse-size
+// and grid-size checks).
+void check_16_contig(const Tensor& t, const char* name, bool f16) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == (f16 ? at::kHalf : at::kBFloat16) && t.is_contiguous(), name,
+              " must be a contiguous ", f16 ? "fp16" : "bf16", " GPU tensor");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
 }
+const uint16_t* u16(const Tensor& t) { return reinterpret_cast<const uint16_t*>(t.data_ptr()); }
+uint16_t* u16_mut(Tensor& t) { return reinterpret_cast<uint16_t*>(t.data_ptr()); }
 
-// qkv [B, S, 3*H*64] -> {ctx [B, S, H*64], lse2 [B*H, stride]}
+// qkv [B, S, 3*H*64] -> {ctx [B, S, H*64], lse2 [B*H, stride]}; stream: attn_stream_kernels.hip
+// (1 <= S <= 4096) instead of attn_kernels.hip (S <= 256)
+std::vector<Tensor> attn_fwd_any(Tensor qkv, int64_t heads, double scale, bool f16, bool stream, const char* fn) {
+  check_16_contig(qkv, "qkv", f16);
+  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, fn, ": qkv must be [B, S, 3*H*64]");
+  const int B = qkv.size(0), S = qkv.size(1), H = heads;
+  if (stream) {
+    TORCH_CHECK(dpt::attn_stream_supported(S, 64), fn, ": needs 1 <= S <= 4096 and head dim 64");
+    TORCH_CHECK((int64_t)B * H * ((S + 31) / 32) < (1LL << 31), fn, ": B * H * S too large for one grid");
+  } else {
+    TORCH_CHECK(dpt::attn_supported(S, 64), fn, ": needs S <= 256 and head dim 64");
+  }
+  auto ctx = at::empty({B, S, H * 64}, qkv.options());
+  auto lse = at::empty({(int64_t)B * H, dpt::attn_lse_stride(S)}, qkv.options().dtype(at::kFloat));
+  if (B * H == 0) return {ctx, lse};  // empty batch: a zero-sized grid is an invalid launch
+  c10::hip::HIPGuard guard(qkv.device().index());
+  auto launch = stream ? (f16 ? dpt::launch_attn_stream_fwd_f16 : dpt::launch_attn_stream_fwd)
+                       : (f16 ? dpt::launch_attn_fwd_f16 : dpt::launch_attn_fwd);
+  launch(u16(qkv), u16_mut(ctx), lse.data_ptr<float>(), B, S, H, (float)scale, cur_stream(qkv));
+  return {ctx, lse};
+}
+
+Tensor attn_bwd_any(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, double scale, bool f16,
+                    bool stream, const char* fn) {
+  check_16_contig(qkv, "qkv", f16);
+  check_16_contig(out, "out", f16);
+  check_16_contig(dout, "grad_output", f16);
+  TORCH_CHECK(qkv.dim() == 3, fn, ": qkv must be [B, S, 3*H*64]");
+  const int B = qkv.size(0), S = qkv.size(1), H = heads;
+  if (stream) {
+    TORCH_CHECK(dpt::attn_stream_supported(S, 64), fn, ": needs 1 <= S <= 4096 and head dim 64");
+  } else {
+    TORCH_CHECK(dpt::attn_supported(S, 64), fn, ": needs S <= 256 and head dim 64");
+  }
+  TORCH_CHECK(out.sizes() == dout.sizes() && out.dim() == 3 && out.size(0) == B && out.size(1) == S &&
+                  out.size(2) == H * 64 && qkv.size(2) == 3 * H * 64, fn, ": shape mismatch");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+                  lse.numel() == (int64_t)B * H * dpt::attn_lse_stride(S), fn, ": bad lse");
+  if (stream) {
+    TORCH_CHECK((int64_t)B * H * ((S + 31) / 32) < (1LL << 31), fn, ": B * H * S too large for one grid");
+  }
+  auto dqkv = at::empty_like(qkv);
+  if (B * H == 0) return dqkv;  // empty batch: nothing to launch
+  c10::hip::HIPGuard guard(qkv.device().index());
+  if (stream) {
+    auto dsum = at::empty_like(lse);  // rowsum(dO * O), written once and read by both gradient kernels
+    (f16 ? dpt::launch_attn_stream_bwd_f16 : dpt::launch_attn_stream_bwd)(
+        u16(qkv), u16(out), u16(dout), lse.data_ptr<float>(), dsum.data_ptr<float>(), u16_mut(dqkv), B, S, H,
+        (float)scale, cur_stream(qkv));
+  } else {
+    (f16 ? dpt::launch_attn_bwd_f16 : dpt::launch_attn_bwd)(u16(qkv), u16(out), u16(dout), lse.data_ptr<float>(),
+                                                            u16_mut(dqkv), B, S, H, (float)scale, cur_stream(qkv));
+  }
+  return dqkv;
+}
+
 std::vector<Tensor> attn_fwd(Tensor qkv, int64_t heads, double scale) {
-  check_bf16_contig(qkv, "qkv");
-  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "attn_fwd: qkv must be [B, S, 3*H*64]");
-  const int B = qkv.size(0), S = qkv.size(1), H = heads;
-  TORCH_CHECK(dpt::attn_supported(S, 64), "attn_fwd: needs S <= 256 and head dim 64");
-  auto ctx = at::empty({B, S, H * 64}, qkv.options());
-  auto lse = at::empty({(int64_t)B * H, dpt::attn_lse_stride(S)}, qkv.options().dtype(at::kFloat));
-  if (B * H == 0) return {ctx, lse};  // empty batch: a zero-sized grid is an invalid launch
-  c10::hip::HIPGuard guard(qkv.device().index());
-  dpt::launch_attn_fwd(reinterpret_cast<const uint16_t*>(qkv.data_ptr()), reinterpret_cast<uint16_t*>(ctx.data_ptr()),
-                       lse.data_ptr<float>(), B, S, H, (float)scale, cur_stream(qkv));
-  return {ctx, lse};
+  return attn_fwd_any(qkv, heads, scale, false, false, "attn_fwd");
 }
-
 Tensor attn_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, double scale) {
-  check_bf16_contig(qkv, "qkv");
-  check_bf16_contig(out, "out");
-  check_bf16_contig(dout, "grad_output");
-  TORCH_CHECK(qkv.dim() == 3, "attn_bwd: qkv must be [B, S, 3*H*64]");
-  const int B = qkv.size(0), S = qkv.size(1), H = heads;
-  TORCH_CHECK(dpt::attn_supported(S, 64), "attn_bwd: needs S <= 256 and head dim 64");
-  TORCH_CHECK(out.sizes() == dout.sizes() && out.dim() == 3 && out.size(0) == B && out.size(1) == S &&
-                  out.size(2) == H * 64 && qkv.size(2) == 3 * H * 64, "attn_bwd: shape mismatch");
-  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
-                  lse.numel() == (int64_t)B * H * dpt::attn_lse_stride(S), "attn_bwd: bad lse");
-  auto dqkv = at::empty_like(qkv);
-  if (B * H == 0) return dqkv;  // empty batch: nothing to launch
-  c10::hip::HIPGuard guard(qkv.device().index());
-  dpt::launch_attn_bwd(reinterpret_cast<const uint16_t*>(qkv.data_ptr()), reinterpret_cast<const uint16_t*>(out.data_ptr()),
-                       reinterpret_cast<const uint16_t*>(dout.data_ptr()), lse.data_ptr<float>(),
-                       reinterpret_cast<uint16_t*>(dqkv.data_ptr()), B, S, H, (float)scale, cur_stream(qkv));
-  return dqkv;
+  return attn_bwd_any(qkv, out, dout, lse, heads, scale, false, false, "attn_bwd");
 }
-
-// The same op on the streaming kernels (attn_stream_kernels.hip): 1 <= S <= 4096.
 std::vector<Tensor> attn_stream_fwd(Tensor qkv, int64_t heads, double scale) {
-  check_bf16_contig(qkv, "qkv");
-  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * heads * 64, "attn_stream_fwd: qkv must be [B, S, 3*H*64]");
-  const int B = qkv.size(0), S = qkv.size(1), H = heads;
-  TORCH_CHECK(dpt::attn_stream_supported(S, 64), "attn_stream_fwd: needs 1 <= S <= 4096 and head dim 64");
-  TORCH_CHECK((int64_t)B * H * ((S + 31) / 32) < (1LL << 31), "attn_stream_fwd: B * H * S too large for one grid");
-  auto ctx = at::empty({B, S, H * 64}, qkv.options());
-  auto lse = at::empty({(int64_t)B * H, dpt::attn_lse_stride(S)}, qkv.options().dtype(at::kFloat));
-  if (B * H == 0) return {ctx, lse};  // empty batch: a zero-sized grid is an invalid launch
-  c10::hip::HIPGuard guard(qkv.device().index());
-  dpt::launch_attn_stream_fwd(reinterpret_cast<const uint16_t*>(qkv.data_ptr()),
-                              reinterpret_cast<uint16_t*>(ctx.data_ptr()), lse.data_ptr<float>(), B, S, H,
-                              (float)scale, cur_stream(qkv));
-  return {ctx, lse};
+  return attn_fwd_any(qkv, heads, scale, false, true, "attn_stream_fwd");
 }
-
 Tensor attn_stream_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, double scale) {
-  check_bf16_contig(qkv, "qkv");
-  check_bf16_contig(out, "out");
-  check_bf16_contig(dout, "grad_output");
-  TORCH_CHECK(qkv.dim() == 3, "attn_stream_bwd: qkv must be [B, S, 3*H*64]");
-  const int B = qkv.size(0), S = qkv.size(1), H = heads;
-  TORCH_CHECK(dpt::attn_stream_supported(S, 64), "attn_stream_bwd: needs 1 <= S <= 4096 and head dim 64");
-  TORCH_CHECK(out.sizes() == dout.sizes() && out.dim() == 3 && out.size(0) == B && out.size(1) == S &&
-                  out.size(2) == H * 64 && qkv.size(2) == 3 * H * 64, "attn_stream_bwd: shape mismatch");
-  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
-                  lse.numel() == (int64_t)B * H * dpt::attn_lse_stride(S), "attn_stream_bwd: bad lse");
-  TORCH_CHECK((int64_t)B * H * ((S + 31) / 32) < (1LL << 31), "attn_stream_bwd: B * H * S too large for one grid");
-  auto dqkv = at::empty_like(qkv);
-  if (B * H == 0) return dqkv;  // empty batch: nothing to launch
-  auto dsum = at::empty_like(lse);  // rowsum(dO * O), written once and read by both gradient kernels
-  c10::hip::HIPGuard guard(qkv.device().index());
-  dpt::launch_attn_stream_bwd(reinterpret_cast<const uint16_t*>(qkv.data_ptr()),
-                              reinterpret_cast<const uint16_t*>(out.data_ptr()),
-                              reinterpret_cast<const uint16_t*>(dout.data_ptr()), lse.data_ptr<float>(),
-                              dsum.data_ptr<float>(), reinterpret_cast<uint16_t*>(dqkv.data_ptr()), B, S, H,
-                              (float)scale, cur_stream(qkv));
-  return dqkv;
+  return attn_bwd_any(qkv, out, dout, lse, heads, scale, false, true, "attn_stream_bwd");
+}
+// fp16 tensors in, fp16 ctx / dqkv and fp32 lse out; a value past fp16's range is +-inf
+std::vector<Tensor> attn_fwd_f16(Tensor qkv, int64_t heads, double scale) {
+  return attn_fwd_any(qkv, heads, scale, true, false, "attn_fwd_f16");
+}
+Tensor attn_bwd_f16(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, double scale) {
+  return attn_bwd_any(qkv, out, dout, lse, heads, scale, true, false, "attn_bwd_f16");
+}
+std::vector<Tensor> attn_stream_fwd_f16(Tensor qkv, int64_t heads, double scale) {
+  return attn_fwd_any(qkv, heads, scale, true, true, "attn_stream_fwd_f16");
+}
+Tensor attn_stream_bwd_f16(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads, double scale) {
+  return attn_bwd_any(qkv, out, dout, lse, heads, scale, true, true, "attn_stream_bwd_f16");
 }
 
 std::tuple<int64_t, int64_t, int64_t> attn_stream_tiles() {
@@ -1643,6 +1654,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_stream_fwd", &attn_stream_fwd, py::arg("qkv"), py::arg("heads"), py::arg("scale"));
   m.def("attn_stream_bwd", &attn_stream_bwd, py::arg("qkv"), py::arg("out"), py::arg("grad_output"), py::arg("lse"),
         py::arg("heads"), py::arg("scale"));
+  m.def("attn_fwd_f16", &attn_fwd_f16, py::arg("qkv"), py::arg("heads"), py::arg("scale"));
+  m.def("attn_bwd_f16", &attn_bwd_f16, py::arg("qkv"), py::arg("out"), py::arg("grad_output"), py::arg("lse"),
+        py::arg("heads"), py::arg("scale"));
+  m.def("attn_stream_fwd_f16", &attn_stream_fwd_f16, py::arg("qkv"), py::arg("heads"), py::arg("scale"));
+  m.def("attn_stream_bwd_f16", &attn_stream_bwd_f16, py::arg("qkv"), py::arg("out"), py::arg("grad_output"),
+        py::arg("lse"), py::arg("heads"), py::arg("scale"));
   m.def("attn_stream_tiles", &attn_stream_tiles,
         "(queries per workgroup, keys per chunk, query rows per backward chunk) of the streaming attention kernels");
   m.def("conv_set_variant", &dpt::conv_set_variant, py::arg("variant"));

@@ -36,6 +36,11 @@ ROCM = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
 ARCH = os.environ.get("DPT_OFFLOAD_ARCH", "gfx950")
 
 HIP_SOURCES = sorted((CSRC / "kernels").glob("*.hip"))
+# Extra hipcc flags of single kernel files, and the .hip files such a file includes (they go
+# into its stamp).  attn_f16_kernels.hip: no packed fp32 arithmetic (v_pk_*_f32) in the fp16
+# attention kernels; the bf16 ones in the files it includes keep the common flags.
+SOURCE_FLAGS = {"attn_f16_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+SOURCE_INCLUDES = {"attn_f16_kernels.hip": ["attn_kernels.hip", "attn_stream_kernels.hip"]}
 CPP_SOURCES = [CSRC / "watchdog.cpp", CSRC / "rccl_comm.cpp", CSRC / "host_comm.cpp", CSRC / "pg_comm.cpp",
                CSRC / "reducer.cpp", CSRC / "bindings.cpp"]
 
@@ -73,6 +78,8 @@ def _stamp(src: Path, flags) -> str:
     h.update(src.read_bytes())
     for hdr in sorted(CSRC.rglob("*.h")):
         h.update(hdr.read_bytes())
+    for inc in SOURCE_INCLUDES.get(src.name, ()):
+        h.update((src.parent / inc).read_bytes())
     return h.hexdigest()[:16]
 
 
@@ -102,7 +109,7 @@ def build(jobs: int = 4, force: bool = False, debug: bool = False, verbose: bool
 
     jobs_list = []
     for src in HIP_SOURCES:
-        jobs_list.append((src, hip_flags))
+        jobs_list.append((src, hip_flags + SOURCE_FLAGS.get(src.name, [])))
     for src in CPP_SOURCES:
         jobs_list.append((src, cpp_flags))
 

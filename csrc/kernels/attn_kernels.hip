@@ -18,6 +18,20 @@
 //             queries): S^T, dP^T, dS^T, dQ^T += K^T dS^T.
 // Padding keys (>= S) are masked to probability 0; padding queries are never stored and get
 // lse2 = +inf in the backward, so they contribute nothing to dK / dV.
+//
+// Element type: every kernel takes `bool F16` (false: bf16, true: fp16 and v_mfma_f32_32x32x16_f16;
+// the fp16 instantiations are compiled in attn_f16_kernels.hip).  Operands are raw 16-bit data in
+// global memory, LDS and fragments either way; only the MFMA (cmfma), the accumulator tile
+// re-used as an operand (acc_frag), the output conversions (attn_store_rows, attn_cvt16) and the
+// unpacking in D (attn_dot8) know the type.  fp16's range is part of the contract:
+//   overflow   an fp32 value that does not fit fp16 - dS as an operand, context / dQ / dK / dV as
+//              outputs - becomes +-inf (v_cvt_pk_f16_f32, no clamp), never 65504: under the loss
+//              scaler dO comes multiplied by up to 2^16, and an overflow has to reach found_inf
+//              so that the step is skipped and the scale halves.
+//   underflow  P and dS below 2^-14 stay fp16 subnormals (absolute rounding error <= 2^-25): the
+//              conversions and the f16 MFMA keep them (measured, tests/test_attention_f16_gpu.py
+//              holds with eta = 2^-25); the kernels do nothing special for them.
+// attn_exp2, the log2-domain lse2 (fp32) and the masking do not depend on the type.
 #include <cmath>
 
 #include "attn_common.h"  // attn::D / RB, attn_exp2, attn_stage (shared with attn_stream_kernels.hip)
@@ -27,7 +41,7 @@
 
 namespace dpt {
 
-template <int NT>
+template <int NT, bool F16>
 __global__ __launch_bounds__(NT * 64) void attn_fwd_kernel(const uint16_t* __restrict__ qkv,
                                                            uint16_t* __restrict__ ctx, float* __restrict__ lse2,
                                                            int S, int H, float scale_log2) {
@@ -60,7 +74,7 @@ __global__ __launch_bounds__(NT * 64) void attn_fwd_kernel(const uint16_t* __res
 #pragma unroll
     for (int e = 0; e < 16; ++e) sc[kt][e] = 0.f;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) sc[kt] = mfma32(row_frag<RB>(kimg, kt * 32 + r, 2 * s + h), qf[s], sc[kt]);
+    for (int s = 0; s < 4; ++s) sc[kt] = cmfma<F16>(row_frag<RB>(kimg, kt * 32 + r, 2 * s + h), qf[s], sc[kt]);
   }
   // softmax over keys (this lane's registers + the other lane half)
   // padding keys exist only in the last tile(s): the per-element mask is a wave-uniform branch
@@ -100,25 +114,14 @@ __global__ __launch_bounds__(NT * 64) void attn_fwd_kernel(const uint16_t* __res
   for (int kt = 0; kt < NT; ++kt)
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
-      const bf16x8_t pf = acc_frag(sc[kt], s2);
+      const bf16x8_t pf = acc_frag<F16>(sc[kt], s2);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
-        o[dt] = mfma32(tr_frag<RB, true>(vimg, kt * 32 + 16 * s2, dt * 32, lane), pf, o[dt]);
+        o[dt] = cmfma<F16>(tr_frag<RB, true>(vimg, kt * 32 + 16 * s2, dt * 32, lane), pf, o[dt]);
     }
   if (q < S) {
     const float inv = 1.0f / l;
-    uint16_t* out = ctx + ((int64_t)b * S + q) * H * D + hh * D;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {  // rows d = 32dt + 8g + 4h + 0..3 (registers 4g..4g+3)
-        const f32x2_t v0 = {o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv};
-        const f32x2_t v1 = {o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv};
-        uint2 pk;
-        pk.x = __builtin_bit_cast(uint32_t, __builtin_convertvector(v0, bf16x2_t));
-        pk.y = __builtin_bit_cast(uint32_t, __builtin_convertvector(v1, bf16x2_t));
-        *reinterpret_cast<uint2*>(out + dt * 32 + 8 * g + 4 * h) = pk;
-      }
+    attn_store_rows<F16>(ctx + ((int64_t)b * S + q) * H * D + hh * D, o, inv, h);
     if (h == 0) lse2[(int64_t)bh * SP + q] = ms + log2f(l);
   }
 }
@@ -130,7 +133,7 @@ __global__ __launch_bounds__(NT * 64) void attn_fwd_kernel(const uint16_t* __res
 #ifndef DPT_ATTN_P1_WAVES  // min waves per SIMD of the split phase-1 kernel (4 = two workgroups per CU)
 #define DPT_ATTN_P1_WAVES 2
 #endif
-template <int NT, int PHASE = 0>
+template <int NT, bool F16, int PHASE = 0>
 __global__ __launch_bounds__(NT * 64, PHASE == 1 ? DPT_ATTN_P1_WAVES : PHASE == 2 ? 4 : 1) void attn_bwd_kernel(const uint16_t* __restrict__ qkv,
                                                                         const uint16_t* __restrict__ out,
                                                                         const uint16_t* __restrict__ dout,
@@ -173,16 +176,9 @@ __global__ __launch_bounds__(NT * 64, PHASE == 1 ? DPT_ATTN_P1_WAVES : PHASE == 
       const uint16_t* po = out + ((int64_t)b * S + t) * ldo + hh * D;
       const uint16_t* pd = dout + ((int64_t)b * S + t) * ldo + hh * D;
 #pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const uint4 a = *reinterpret_cast<const uint4*>(po + c * 8);
-        const uint4 g = *reinterpret_cast<const uint4*>(pd + c * 8);
-        const uint32_t ua[4] = {a.x, a.y, a.z, a.w}, ug[4] = {g.x, g.y, g.z, g.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          acc = __builtin_fmaf(bf16_to_f32(ua[k] & 0xffff), bf16_to_f32(ug[k] & 0xffff), acc);
-          acc = __builtin_fmaf(bf16_to_f32(ua[k] >> 16), bf16_to_f32(ug[k] >> 16), acc);
-        }
-      }
+      for (int c = 0; c < 8; ++c)
+        acc = attn_dot8<F16>(*reinterpret_cast<const uint4*>(po + c * 8), *reinterpret_cast<const uint4*>(pd + c * 8),
+                             acc);
     }
     dd[t] = acc;
     ls[t] = t < S ? lse2[(int64_t)bh * SP + t] : INFINITY;
@@ -215,8 +211,8 @@ __global__ __launch_bounds__(NT * 64, PHASE == 1 ? DPT_ATTN_P1_WAVES : PHASE == 
       for (int e = 0; e < 16; ++e) { sc[e] = 0.f; dp[e] = 0.f; }
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        sc = mfma32(row_frag<RB>(qimg, qt * 32 + r, 2 * s + h), kf[s], sc);   // S = Q K^T
-        dp = mfma32(row_frag<RB>(oimg, qt * 32 + r, 2 * s + h), vf[s], dp);   // dP = dO V^T
+        sc = cmfma<F16>(row_frag<RB>(qimg, qt * 32 + r, 2 * s + h), kf[s], sc);   // S = Q K^T
+        dp = cmfma<F16>(row_frag<RB>(oimg, qt * 32 + r, 2 * s + h), vf[s], dp);   // dP = dO V^T
       }
       // rows = queries, column = this lane's key: rows (e & 3) of group e >> 2 are 4 consecutive
       // queries, so their lse2 / D values come in one 16-byte LDS read each (8 reads, not 32)
@@ -236,11 +232,11 @@ __global__ __launch_bounds__(NT * 64, PHASE == 1 ? DPT_ATTN_P1_WAVES : PHASE == 
       }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
-        const bf16x8_t pa = acc_frag(sc, s2), da = acc_frag(dp, s2);
+        const bf16x8_t pa = acc_frag<F16>(sc, s2), da = acc_frag<F16>(dp, s2);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
-          dv[dt] = mfma32(pa, tr_frag<RB, true>(oimg, qt * 32 + 16 * s2, dt * 32, lane), dv[dt]);  // P^T dO
-          dk[dt] = mfma32(da, tr_frag<RB, true>(qimg, qt * 32 + 16 * s2, dt * 32, lane), dk[dt]);  // dS^T Q
+          dv[dt] = cmfma<F16>(pa, tr_frag<RB, true>(oimg, qt * 32 + 16 * s2, dt * 32, lane), dv[dt]);  // P^T dO
+          dk[dt] = cmfma<F16>(da, tr_frag<RB, true>(qimg, qt * 32 + 16 * s2, dt * 32, lane), dk[dt]);  // dS^T Q
         }
       }
     }
@@ -252,8 +248,8 @@ __global__ __launch_bounds__(NT * 64, PHASE == 1 ? DPT_ATTN_P1_WAVES : PHASE == 
         const int kk = k0 + (e & 3) + 8 * (e >> 2) + 4 * h;
         if (kk < S) {
           uint16_t* row = dqkv + ((int64_t)b * S + kk) * ld;
-          row[(int64_t)(H + hh) * D + dt * 32 + r] = f32_to_bf16(dk[dt][e] * scale);
-          row[(int64_t)(2 * H + hh) * D + dt * 32 + r] = f32_to_bf16(dv[dt][e]);
+          row[(int64_t)(H + hh) * D + dt * 32 + r] = attn_cvt16<F16>(dk[dt][e] * scale);
+          row[(int64_t)(2 * H + hh) * D + dt * 32 + r] = attn_cvt16<F16>(dv[dt][e]);
         }
       }
   }
@@ -284,8 +280,8 @@ __global__ __launch_bounds__(NT * 64, PHASE == 1 ? DPT_ATTN_P1_WAVES : PHASE == 
       for (int e = 0; e < 16; ++e) { st[e] = 0.f; dpt[e] = 0.f; }
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        st = mfma32(row_frag<RB>(kimg, kt * 32 + r, 2 * s + h), qf[s], st);
-        dpt = mfma32(row_frag<RB>(vimg, kt * 32 + r, 2 * s + h), of[s], dpt);
+        st = cmfma<F16>(row_frag<RB>(kimg, kt * 32 + r, 2 * s + h), qf[s], st);
+        dpt = cmfma<F16>(row_frag<RB>(vimg, kt * 32 + r, 2 * s + h), of[s], dpt);
       }
 #pragma unroll
       for (int e = 0; e < 16; ++e) {  // rows = keys, column = this lane's query
@@ -295,72 +291,89 @@ __global__ __launch_bounds__(NT * 64, PHASE == 1 ? DPT_ATTN_P1_WAVES : PHASE == 
       }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
-        const bf16x8_t df = acc_frag(st, s2);
+        const bf16x8_t df = acc_frag<F16>(st, s2);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
-          dq[dt] = mfma32(tr_frag<RB, true>(kimg, kt * 32 + 16 * s2, dt * 32, lane), df, dq[dt]);  // K^T dS^T
+          dq[dt] = cmfma<F16>(tr_frag<RB, true>(kimg, kt * 32 + 16 * s2, dt * 32, lane), df, dq[dt]);  // K^T dS^T
       }
     }
-    if (q < S) {
-      uint16_t* row = dqkv + ((int64_t)b * S + q) * ld + (int64_t)hh * D;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x2_t v0 = {dq[dt][4 * g] * scale, dq[dt][4 * g + 1] * scale};
-          const f32x2_t v1 = {dq[dt][4 * g + 2] * scale, dq[dt][4 * g + 3] * scale};
-          uint2 pk;
-          pk.x = __builtin_bit_cast(uint32_t, __builtin_convertvector(v0, bf16x2_t));
-          pk.y = __builtin_bit_cast(uint32_t, __builtin_convertvector(v1, bf16x2_t));
-          *reinterpret_cast<uint2*>(row + dt * 32 + 8 * g + 4 * h) = pk;
-        }
-    }
+    if (q < S) attn_store_rows<F16>(dqkv + ((int64_t)b * S + q) * ld + (int64_t)hh * D, dq, scale, h);
   }
 }
 
-bool attn_supported(int S, int Dh) { return Dh == attn::D && S >= 1 && S <= 256; }
-
-int attn_lse_stride(int S) { return (S + 31) / 32 * 32; }
-
+// Launches of either element type: the same tile-count dispatch and the same 7-tile phase split.
 #define DPT_ATTN_DISPATCH(NTV, KERNEL, ...)                                                              \
   switch (NTV) {                                                                                         \
-    case 1: hipLaunchKernelGGL(KERNEL<1>, grid, dim3(64), 0, st, __VA_ARGS__); break;                    \
-    case 2: hipLaunchKernelGGL(KERNEL<2>, grid, dim3(128), 0, st, __VA_ARGS__); break;                   \
-    case 3: hipLaunchKernelGGL(KERNEL<3>, grid, dim3(192), 0, st, __VA_ARGS__); break;                   \
-    case 4: hipLaunchKernelGGL(KERNEL<4>, grid, dim3(256), 0, st, __VA_ARGS__); break;                   \
-    case 5: hipLaunchKernelGGL(KERNEL<5>, grid, dim3(320), 0, st, __VA_ARGS__); break;                   \
-    case 6: hipLaunchKernelGGL(KERNEL<6>, grid, dim3(384), 0, st, __VA_ARGS__); break;                   \
-    case 7: hipLaunchKernelGGL(KERNEL<7>, grid, dim3(448), 0, st, __VA_ARGS__); break;                   \
-    default: hipLaunchKernelGGL(KERNEL<8>, grid, dim3(512), 0, st, __VA_ARGS__); break;                  \
+    case 1: hipLaunchKernelGGL((KERNEL<1, F16>), grid, dim3(64), 0, st, __VA_ARGS__); break;             \
+    case 2: hipLaunchKernelGGL((KERNEL<2, F16>), grid, dim3(128), 0, st, __VA_ARGS__); break;            \
+    case 3: hipLaunchKernelGGL((KERNEL<3, F16>), grid, dim3(192), 0, st, __VA_ARGS__); break;            \
+    case 4: hipLaunchKernelGGL((KERNEL<4, F16>), grid, dim3(256), 0, st, __VA_ARGS__); break;            \
+    case 5: hipLaunchKernelGGL((KERNEL<5, F16>), grid, dim3(320), 0, st, __VA_ARGS__); break;            \
+    case 6: hipLaunchKernelGGL((KERNEL<6, F16>), grid, dim3(384), 0, st, __VA_ARGS__); break;            \
+    case 7: hipLaunchKernelGGL((KERNEL<7, F16>), grid, dim3(448), 0, st, __VA_ARGS__); break;            \
+    default: hipLaunchKernelGGL((KERNEL<8, F16>), grid, dim3(512), 0, st, __VA_ARGS__); break;           \
   }
 
-void launch_attn_fwd(const uint16_t* qkv, uint16_t* ctx, float* lse2, int B, int S, int H, float scale,
-                     hipStream_t st) {
+template <bool F16>
+static void attn_fwd_launch(const uint16_t* qkv, uint16_t* ctx, float* lse2, int B, int S, int H, float scale,
+                            hipStream_t st) {
   const int nt = (S + 31) / 32;
   const dim3 grid((unsigned)(B * H));
   const float sl2 = scale * 1.4426950408889634f;
   DPT_ATTN_DISPATCH(nt, attn_fwd_kernel, qkv, ctx, lse2, S, H, sl2)
 }
 
-// Split by default for 7 query / key tiles (ViT-B/16, 197 tokens): 214-224 -> 194-202 us per
-// call at batch 128 x 12 heads, bitwise identical (bench/attn_bwd_ab.py).  The phase-2 kernel
-// holds two workgroups per CU (128 VGPRs); phase 1 stays at 168 VGPRs (at 128 it spills: 262 us).
-static int g_attn_bwd_split = 1;
-void attn_set_bwd_split(int on) { g_attn_bwd_split = on; }
-
-void launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse2,
-                     uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st) {
+template <bool F16>
+static void attn_bwd_launch(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse2,
+                            uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st) {
   const int nt = (S + 31) / 32;
   const dim3 grid((unsigned)(B * H));
   const float sl2 = scale * 1.4426950408889634f;
-  if (g_attn_bwd_split && nt == 7) {  // ViT-B/16 (197 tokens)
-    hipLaunchKernelGGL((attn_bwd_kernel<7, 1>), grid, dim3(448), 0, st, qkv, out, dout, lse2, dqkv, S, H, sl2, scale);
-    hipLaunchKernelGGL((attn_bwd_kernel<7, 2>), grid, dim3(448), 0, st, qkv, out, dout, lse2, dqkv, S, H, sl2, scale);
+  if (attn_get_bwd_split() && nt == 7) {  // ViT-B/16 (197 tokens)
+    hipLaunchKernelGGL((attn_bwd_kernel<7, F16, 1>), grid, dim3(448), 0, st, qkv, out, dout, lse2, dqkv, S, H, sl2, scale);
+    hipLaunchKernelGGL((attn_bwd_kernel<7, F16, 2>), grid, dim3(448), 0, st, qkv, out, dout, lse2, dqkv, S, H, sl2, scale);
     return;
   }
   DPT_ATTN_DISPATCH(nt, attn_bwd_kernel, qkv, out, dout, lse2, dqkv, S, H, sl2, scale)
 }
 
 #undef DPT_ATTN_DISPATCH
+
+#ifndef DPT_ATTN_F16_UNIT  // the bf16 unit also owns what does not depend on the element type
+
+bool attn_supported(int S, int Dh) { return Dh == attn::D && S >= 1 && S <= 256; }
+
+int attn_lse_stride(int S) { return (S + 31) / 32 * 32; }
+
+// Split by default for 7 query / key tiles (ViT-B/16, 197 tokens): 214-224 -> 194-202 us per
+// call at batch 128 x 12 heads, bitwise identical (bench/attn_bwd_ab.py).  The phase-2 kernel
+// holds two workgroups per CU (128 VGPRs); phase 1 stays at 168 VGPRs (at 128 it spills: 262 us).
+static int g_attn_bwd_split = 1;
+void attn_set_bwd_split(int on) { g_attn_bwd_split = on; }
+int attn_get_bwd_split() { return g_attn_bwd_split; }
+
+void launch_attn_fwd(const uint16_t* qkv, uint16_t* ctx, float* lse2, int B, int S, int H, float scale,
+                     hipStream_t st) {
+  attn_fwd_launch<false>(qkv, ctx, lse2, B, S, H, scale, st);
+}
+
+void launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse2,
+                     uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st) {
+  attn_bwd_launch<false>(qkv, out, dout, lse2, dqkv, B, S, H, scale, st);
+}
+
+#else  // attn_f16_kernels.hip: the fp16 instantiations
+
+void launch_attn_fwd_f16(const uint16_t* qkv, uint16_t* ctx, float* lse2, int B, int S, int H, float scale,
+                         hipStream_t st) {
+  attn_fwd_launch<true>(qkv, ctx, lse2, B, S, H, scale, st);
+}
+
+void launch_attn_bwd_f16(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse2,
+                         uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st) {
+  attn_bwd_launch<true>(qkv, out, dout, lse2, dqkv, B, S, H, scale, st);
+}
+
+#endif
 
 }  // namespace dpt

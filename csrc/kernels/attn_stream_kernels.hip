@@ -23,6 +23,8 @@
 // Padding keys (>= S) exist only in the last chunk and are masked to probability 0 before the
 // max (forward) and ahead of the exponential (backward); padding queries are never stored and
 // get lse2 = +inf in the backward, so they add nothing to dK / dV.
+// `bool F16` on every kernel: bf16 or fp16 elements, with attn_kernels.hip's range semantics for
+// fp16 (overflow to +-inf, never clamped; P / dS below 2^-14 kept as subnormals).
 #include <cmath>
 
 #include "attn_common.h"
@@ -48,23 +50,9 @@ __device__ __forceinline__ bf16x8_t attn_stream_gfrag(const uint16_t* src, int64
   return __builtin_bit_cast(bf16x8_t, v);
 }
 
-// 32 queries (this lane's column) x 64 dims (registers of two tiles) -> [.., S, .., 64] rows
-__device__ __forceinline__ void attn_stream_store_rows(uint16_t* row, const f32x16_t (&x)[2], float f, int h) {
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {  // rows d = 32dt + 8g + 4h + 0..3 (registers 4g..4g+3)
-      const f32x2_t v0 = {x[dt][4 * g] * f, x[dt][4 * g + 1] * f};
-      const f32x2_t v1 = {x[dt][4 * g + 2] * f, x[dt][4 * g + 3] * f};
-      uint2 pk;
-      pk.x = __builtin_bit_cast(uint32_t, __builtin_convertvector(v0, bf16x2_t));
-      pk.y = __builtin_bit_cast(uint32_t, __builtin_convertvector(v1, bf16x2_t));
-      *reinterpret_cast<uint2*>(row + dt * 32 + 8 * g + 4 * h) = pk;
-    }
-}
-
 // grid: (B*H) * nqb workgroups, block = bh * nqb + query block
 // (two waves per SIMD: left to itself the compiler takes 274 registers and one)
+template <bool F16>
 __global__ __launch_bounds__(attn_stream::NTH, 2) void attn_stream_fwd_kernel(const uint16_t* __restrict__ qkv,
                                                                               uint16_t* __restrict__ ctx,
                                                                               float* __restrict__ lse2, int S, int H,
@@ -112,7 +100,7 @@ __global__ __launch_bounds__(attn_stream::NTH, 2) void attn_stream_fwd_kernel(co
 #pragma unroll
         for (int e = 0; e < 16; ++e) sc[kt][e] = 0.f;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) sc[kt] = mfma32(row_frag<RB>(kimg, kt * 32 + r, 2 * s + h), qf[s], sc[kt]);
+        for (int s = 0; s < 4; ++s) sc[kt] = cmfma<F16>(row_frag<RB>(kimg, kt * 32 + r, 2 * s + h), qf[s], sc[kt]);
         if (c0 + (kt + 1) * 32 > S) {  // padding keys: only in the last tile of the last chunk
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
@@ -154,22 +142,23 @@ __global__ __launch_bounds__(attn_stream::NTH, 2) void attn_stream_fwd_kernel(co
       if (kt < nkt) {
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-          const bf16x8_t pf = acc_frag(sc[kt], s2);
+          const bf16x8_t pf = acc_frag<F16>(sc[kt], s2);
 #pragma unroll
           for (int dt = 0; dt < 2; ++dt)
-            o[dt] = mfma32(tr_frag<RB, true>(vimg, kt * 32 + 16 * s2, dt * 32, lane), pf, o[dt]);
+            o[dt] = cmfma<F16>(tr_frag<RB, true>(vimg, kt * 32 + 16 * s2, dt * 32, lane), pf, o[dt]);
         }
       }
     }
   }
   if (q < S) {
-    attn_stream_store_rows(ctx + ((int64_t)b * S + q) * H * D + hh * D, o, 1.0f / l, h);
+    attn_store_rows<F16>(ctx + ((int64_t)b * S + q) * H * D + hh * D, o, 1.0f / l, h);
     if (h == 0) lse2[(int64_t)bh * stride + q] = m * scale_log2 + log2f(l);
   }
 }
 
 // D[q] = sum_d dO * O (fp32, from the bf16 output): 8 lanes per [64]-row, one 16-byte load of
 // each operand per lane; rows = B*S*H in memory order, dsum [B*H, stride]
+template <bool F16>
 __global__ __launch_bounds__(256) void attn_stream_dsum_kernel(const uint16_t* __restrict__ out,
                                                                const uint16_t* __restrict__ dout,
                                                                float* __restrict__ dsum, int S, int H, int stride,
@@ -180,12 +169,7 @@ __global__ __launch_bounds__(256) void attn_stream_dsum_kernel(const uint16_t* _
   if (g < rows) {
     const uint4 a = *reinterpret_cast<const uint4*>(out + g * 64 + c * 8);
     const uint4 d = *reinterpret_cast<const uint4*>(dout + g * 64 + c * 8);
-    const uint32_t ua[4] = {a.x, a.y, a.z, a.w}, ud[4] = {d.x, d.y, d.z, d.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      acc = __builtin_fmaf(bf16_to_f32(ua[k] & 0xffff), bf16_to_f32(ud[k] & 0xffff), acc);
-      acc = __builtin_fmaf(bf16_to_f32(ua[k] >> 16), bf16_to_f32(ud[k] >> 16), acc);
-    }
+    acc = attn_dot8<F16>(a, d, acc);
   }
   acc += __shfl_xor(acc, 1, 64);
   acc += __shfl_xor(acc, 2, 64);
@@ -200,6 +184,7 @@ __global__ __launch_bounds__(256) void attn_stream_dsum_kernel(const uint16_t* _
 }
 
 // dK / dV: grid (B*H) * nkb workgroups, block = bh * nkb + key block; wave = 32 keys
+template <bool F16>
 __global__ __launch_bounds__(attn_stream::NTH) void attn_stream_dkdv_kernel(
     const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout, const float* __restrict__ lse2,
     const float* __restrict__ dsum, uint16_t* __restrict__ dqkv, int S, int H, int nkb, int stride,
@@ -252,8 +237,8 @@ __global__ __launch_bounds__(attn_stream::NTH) void attn_stream_dkdv_kernel(
       for (int e = 0; e < 16; ++e) { sc[e] = 0.f; dp[e] = 0.f; }
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        sc = mfma32(row_frag<RB>(qimg, qt * 32 + r, 2 * s + h), kf[s], sc);   // S = Q K^T
-        dp = mfma32(row_frag<RB>(oimg, qt * 32 + r, 2 * s + h), vf[s], dp);   // dP = dO V^T
+        sc = cmfma<F16>(row_frag<RB>(qimg, qt * 32 + r, 2 * s + h), kf[s], sc);   // S = Q K^T
+        dp = cmfma<F16>(row_frag<RB>(oimg, qt * 32 + r, 2 * s + h), vf[s], dp);   // dP = dO V^T
       }
       // rows = queries, column = this lane's key: rows (e & 3) of group e >> 2 are 4 consecutive
       // queries, so their lse2 / D values come in one 16-byte LDS read each
@@ -273,11 +258,11 @@ __global__ __launch_bounds__(attn_stream::NTH) void attn_stream_dkdv_kernel(
       }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
-        const bf16x8_t pa = acc_frag(sc, s2), da = acc_frag(dp, s2);
+        const bf16x8_t pa = acc_frag<F16>(sc, s2), da = acc_frag<F16>(dp, s2);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
-          dv[dt] = mfma32(pa, tr_frag<RB, true>(oimg, qt * 32 + 16 * s2, dt * 32, lane), dv[dt]);  // P^T dO
-          dk[dt] = mfma32(da, tr_frag<RB, true>(qimg, qt * 32 + 16 * s2, dt * 32, lane), dk[dt]);  // dS^T Q
+          dv[dt] = cmfma<F16>(pa, tr_frag<RB, true>(oimg, qt * 32 + 16 * s2, dt * 32, lane), dv[dt]);  // P^T dO
+          dk[dt] = cmfma<F16>(da, tr_frag<RB, true>(qimg, qt * 32 + 16 * s2, dt * 32, lane), dk[dt]);  // dS^T Q
         }
       }
     }
@@ -291,13 +276,14 @@ __global__ __launch_bounds__(attn_stream::NTH) void attn_stream_dkdv_kernel(
       const int kk = k0 + (e & 3) + 8 * (e >> 2) + 4 * h;
       if (kk < S) {
         uint16_t* row = dqkv + ((int64_t)b * S + kk) * ld;
-        row[(int64_t)(H + hh) * D + dt * 32 + r] = f32_to_bf16(dk[dt][e] * scale);
-        row[(int64_t)(2 * H + hh) * D + dt * 32 + r] = f32_to_bf16(dv[dt][e]);
+        row[(int64_t)(H + hh) * D + dt * 32 + r] = attn_cvt16<F16>(dk[dt][e] * scale);
+        row[(int64_t)(2 * H + hh) * D + dt * 32 + r] = attn_cvt16<F16>(dv[dt][e]);
       }
     }
 }
 
 // dQ: grid (B*H) * nqb workgroups, block = bh * nqb + query block; wave = 32 queries
+template <bool F16>
 __global__ __launch_bounds__(attn_stream::NTH) void attn_stream_dq_kernel(
     const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout, const float* __restrict__ lse2,
     const float* __restrict__ dsum, uint16_t* __restrict__ dqkv, int S, int H, int nqb, int stride,
@@ -345,8 +331,8 @@ __global__ __launch_bounds__(attn_stream::NTH) void attn_stream_dq_kernel(
       for (int e = 0; e < 16; ++e) { st[e] = 0.f; dpt[e] = 0.f; }
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        st = mfma32(row_frag<RB>(kimg, kt * 32 + r, 2 * s + h), qf[s], st);
-        dpt = mfma32(row_frag<RB>(vimg, kt * 32 + r, 2 * s + h), of[s], dpt);
+        st = cmfma<F16>(row_frag<RB>(kimg, kt * 32 + r, 2 * s + h), qf[s], st);
+        dpt = cmfma<F16>(row_frag<RB>(vimg, kt * 32 + r, 2 * s + h), of[s], dpt);
       }
 #pragma unroll
       for (int e = 0; e < 16; ++e) {  // rows = keys, column = this lane's query
@@ -356,15 +342,44 @@ __global__ __launch_bounds__(attn_stream::NTH) void attn_stream_dq_kernel(
       }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
-        const bf16x8_t df = acc_frag(st, s2);
+        const bf16x8_t df = acc_frag<F16>(st, s2);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
-          dq[dt] = mfma32(tr_frag<RB, true>(kimg, kt * 32 + 16 * s2, dt * 32, lane), df, dq[dt]);  // K^T dS^T
+          dq[dt] = cmfma<F16>(tr_frag<RB, true>(kimg, kt * 32 + 16 * s2, dt * 32, lane), df, dq[dt]);  // K^T dS^T
       }
     }
   }
-  if (q < S) attn_stream_store_rows(dqkv + ((int64_t)b * S + q) * ld + (int64_t)hh * D, dq, scale, h);
+  if (q < S) attn_store_rows<F16>(dqkv + ((int64_t)b * S + q) * ld + (int64_t)hh * D, dq, scale, h);
 }
+
+template <bool F16>
+static void attn_stream_fwd_launch(const uint16_t* qkv, uint16_t* ctx, float* lse2, int B, int S, int H,
+                                   float scale, hipStream_t st) {
+  using namespace attn_stream;
+  const int nqb = (S + QB - 1) / QB;
+  const float sl2 = scale * 1.4426950408889634f;
+  hipLaunchKernelGGL(attn_stream_fwd_kernel<F16>, dim3((unsigned)(B * H * nqb)), dim3(NTH), 0, st, qkv, ctx, lse2, S,
+                     H, nqb, attn_lse_stride(S), sl2);
+}
+
+template <bool F16>
+static void attn_stream_bwd_launch(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout,
+                                   const float* lse2, float* dsum, uint16_t* dqkv, int B, int S, int H, float scale,
+                                   hipStream_t st) {
+  using namespace attn_stream;
+  const int nb = (S + QB - 1) / QB, stride = attn_lse_stride(S);
+  const float sl2 = scale * 1.4426950408889634f;
+  const int64_t rows = (int64_t)B * S * H;
+  hipLaunchKernelGGL(attn_stream_dsum_kernel<F16>, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, st, out,
+                     dout, dsum, S, H, stride, rows);
+  const dim3 grid((unsigned)(B * H * nb));
+  hipLaunchKernelGGL(attn_stream_dkdv_kernel<F16>, grid, dim3(NTH), 0, st, qkv, dout, lse2, dsum, dqkv, S, H, nb,
+                     stride, sl2, scale);
+  hipLaunchKernelGGL(attn_stream_dq_kernel<F16>, grid, dim3(NTH), 0, st, qkv, dout, lse2, dsum, dqkv, S, H, nb,
+                     stride, sl2, scale);
+}
+
+#ifndef DPT_ATTN_F16_UNIT  // the bf16 unit also owns what does not depend on the element type
 
 bool attn_stream_supported(int S, int Dh) { return Dh == attn::D && S >= 1 && S <= attn_stream::MAX_S; }
 
@@ -376,26 +391,26 @@ void attn_stream_tiles(int* queries_per_wg, int* keys_per_chunk, int* query_rows
 
 void launch_attn_stream_fwd(const uint16_t* qkv, uint16_t* ctx, float* lse2, int B, int S, int H, float scale,
                             hipStream_t st) {
-  using namespace attn_stream;
-  const int nqb = (S + QB - 1) / QB;
-  const float sl2 = scale * 1.4426950408889634f;
-  hipLaunchKernelGGL(attn_stream_fwd_kernel, dim3((unsigned)(B * H * nqb)), dim3(NTH), 0, st, qkv, ctx, lse2, S, H,
-                     nqb, attn_lse_stride(S), sl2);
+  attn_stream_fwd_launch<false>(qkv, ctx, lse2, B, S, H, scale, st);
 }
 
 void launch_attn_stream_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse2,
                             float* dsum, uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st) {
-  using namespace attn_stream;
-  const int nb = (S + QB - 1) / QB, stride = attn_lse_stride(S);
-  const float sl2 = scale * 1.4426950408889634f;
-  const int64_t rows = (int64_t)B * S * H;
-  hipLaunchKernelGGL(attn_stream_dsum_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, st, out, dout,
-                     dsum, S, H, stride, rows);
-  const dim3 grid((unsigned)(B * H * nb));
-  hipLaunchKernelGGL(attn_stream_dkdv_kernel, grid, dim3(NTH), 0, st, qkv, dout, lse2, dsum, dqkv, S, H, nb, stride,
-                     sl2, scale);
-  hipLaunchKernelGGL(attn_stream_dq_kernel, grid, dim3(NTH), 0, st, qkv, dout, lse2, dsum, dqkv, S, H, nb, stride,
-                     sl2, scale);
+  attn_stream_bwd_launch<false>(qkv, out, dout, lse2, dsum, dqkv, B, S, H, scale, st);
 }
+
+#else  // attn_f16_kernels.hip: the fp16 instantiations
+
+void launch_attn_stream_fwd_f16(const uint16_t* qkv, uint16_t* ctx, float* lse2, int B, int S, int H, float scale,
+                                hipStream_t st) {
+  attn_stream_fwd_launch<true>(qkv, ctx, lse2, B, S, H, scale, st);
+}
+
+void launch_attn_stream_bwd_f16(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse2,
+                                float* dsum, uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t st) {
+  attn_stream_bwd_launch<true>(qkv, out, dout, lse2, dsum, dqkv, B, S, H, scale, st);
+}
+
+#endif
 
 }  // namespace dpt

@@ -384,10 +384,16 @@ void launch_conv_wt_flip(const uint16_t* w, uint16_t* wt, int Cout, int R, int S
 bool attn_supported(int S, int Dh);
 int attn_lse_stride(int S);
 void attn_set_bwd_split(int on);  // attention backward as two phase kernels (A/B)
+int attn_get_bwd_split();
 void launch_attn_fwd(const uint16_t* qkv, uint16_t* ctx, float* lse2, int B, int S, int H, float scale,
                      hipStream_t s);
 void launch_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse2,
                      uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t s);
+// attn_f16_kernels.hip: the same kernels and layouts with fp16 elements (lse2 stays fp32)
+void launch_attn_fwd_f16(const uint16_t* qkv, uint16_t* ctx, float* lse2, int B, int S, int H, float scale,
+                         hipStream_t s);
+void launch_attn_bwd_f16(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse2,
+                         uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t s);
 
 // attn_stream_kernels.hip: the same op for 1 <= S <= 4096 (head dim 64), the other side of each
 // product streamed through LDS in chunks.  Same layouts; dsum [B*H][attn_lse_stride(S)] fp32 is
@@ -399,6 +405,10 @@ void launch_attn_stream_fwd(const uint16_t* qkv, uint16_t* ctx, float* lse2, int
                             hipStream_t s);
 void launch_attn_stream_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse2,
                             float* dsum, uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t s);
+void launch_attn_stream_fwd_f16(const uint16_t* qkv, uint16_t* ctx, float* lse2, int B, int S, int H, float scale,
+                                hipStream_t s);
+void launch_attn_stream_bwd_f16(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse2,
+                                float* dsum, uint16_t* dqkv, int B, int S, int H, float scale, hipStream_t s);
 
 // conv_f32_kernels.hip: channels_last fp32 convolutions on v_mfma_f32_32x32x2_f32 (exact fp32,
 // deterministic split-K).  dgrad = true: a is dy [N,Ho,Wo,Co], b the transposed weight

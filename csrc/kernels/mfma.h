@@ -99,5 +99,19 @@ __device__ __forceinline__ bf16x8_t acc_frag(const f32x16_t& x, int s) {
   }
   return f;
 }
+// The same for either 16-bit type (the fragment stays raw 16-bit data; only the rounding differs).
+// F16: v_cvt_pk_f16_f32 - a value past 65504 becomes +-inf and one below 2^-14 a subnormal.
+template <bool F16>
+__device__ __forceinline__ bf16x8_t acc_frag(const f32x16_t& x, int s) {
+  if constexpr (!F16) return acc_frag(x, s);
+  typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+  u32x4_t f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const f32x2_t v = {x[8 * s + 2 * j], x[8 * s + 2 * j + 1]};
+    f[j] = cpack<true>(v);
+  }
+  return __builtin_bit_cast(bf16x8_t, f);
+}
 
 }  // namespace dpt

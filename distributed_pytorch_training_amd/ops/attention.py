@@ -1,7 +1,7 @@
 """Fused self-attention autograd op on the gfx950 MFMA kernels (csrc/kernels/attn_kernels.hip,
 csrc/kernels/attn_stream_kernels.hip).
 
-``attention(qkv, heads)`` takes the QKV projection output ``[B, S, 3*H*64]`` (bf16) and returns
+``attention(qkv, heads)`` takes the QKV projection output ``[B, S, 3*H*64]`` (bf16 or fp16) and returns
 the merged context ``[B, S, H*64]``: softmax(Q K^T / sqrt(64)) V per head, computed by one
 workgroup per (image, head) with the whole head on chip.  It replaces head split + SDPA + head
 merge of the unfused path (``F.scaled_dot_product_attention`` -> aotriton flash kernels plus
@@ -12,6 +12,11 @@ Up to 256 tokens the whole head sits on chip (``supported``).  Longer sequences,
 (ViT-B/16 above 256 px), run the streaming kernels, which keep one side of each product in
 registers and pass the other through LDS in chunks (``supported_streaming``; ``DPT_NATIVE_ATTN_LONG=0``
 sends them back to SDPA).  ``attention`` picks by sequence length.
+
+fp16 (``--amp``'s default dtype) runs the same kernels instantiated for fp16 (``supported_f16``,
+``supported_streaming_f16``; the ``*_f16`` bindings).  Its range is the caller's business, as with
+SDPA: a context or gradient element past 65504 comes back as +-inf - under the loss scaler that is
+what trips ``found_inf`` and halves the scale - and values below 2^-14 are kept as subnormals.
 """
 from __future__ import annotations
 
@@ -26,19 +31,40 @@ ENABLED = os.environ.get("DPT_NATIVE_ATTN", "1") != "0"
 STREAMING = os.environ.get("DPT_NATIVE_ATTN_LONG", "1") != "0"   # sequences of 257 .. 4096 tokens
 
 
-def supported(qkv: torch.Tensor, heads: int) -> bool:
-    if not (ENABLED and qkv.is_cuda and native_available() and qkv.dtype == torch.bfloat16 and qkv.dim() == 3):
+def _on_chip(qkv: torch.Tensor, heads: int, dtype: torch.dtype) -> bool:
+    if not (ENABLED and qkv.is_cuda and native_available() and qkv.dtype == dtype and qkv.dim() == 3):
         return False
     b, s, d3 = qkv.shape
     return d3 == 3 * heads * 64 and 1 <= s <= 256
 
 
-def supported_streaming(qkv: torch.Tensor, heads: int) -> bool:
-    if not (ENABLED and STREAMING and qkv.is_cuda and native_available() and qkv.dtype == torch.bfloat16
+def _streaming(qkv: torch.Tensor, heads: int, dtype: torch.dtype) -> bool:
+    if not (ENABLED and STREAMING and qkv.is_cuda and native_available() and qkv.dtype == dtype
             and qkv.dim() == 3):
         return False
     b, s, d3 = qkv.shape
     return d3 == 3 * heads * 64 and 256 < s <= 4096
+
+
+def supported(qkv: torch.Tensor, heads: int) -> bool:
+    return _on_chip(qkv, heads, torch.bfloat16)
+
+
+def supported_streaming(qkv: torch.Tensor, heads: int) -> bool:
+    return _streaming(qkv, heads, torch.bfloat16)
+
+
+def supported_f16(qkv: torch.Tensor, heads: int) -> bool:
+    return _on_chip(qkv, heads, torch.float16) and hasattr(native(), "attn_bwd_f16")
+
+
+def supported_streaming_f16(qkv: torch.Tensor, heads: int) -> bool:
+    return _streaming(qkv, heads, torch.float16) and hasattr(native(), "attn_stream_bwd_f16")
+
+
+def _binding(name: str, dtype: torch.dtype):
+    """The entry point for this element type; a missing one is an AttributeError, never a fall-back."""
+    return getattr(native(), name + "_f16" if dtype == torch.float16 else name)
 
 
 class _Attention(torch.autograd.Function):
@@ -46,7 +72,7 @@ class _Attention(torch.autograd.Function):
     def forward(ctx, qkv, heads: int):
         qkv = qkv.contiguous()
         scale = 1.0 / math.sqrt(64)
-        out, lse = native().attn_fwd(qkv, heads, scale)
+        out, lse = _binding("attn_fwd", qkv.dtype)(qkv, heads, scale)
         ctx.save_for_backward(qkv, out, lse)
         ctx.heads, ctx.scale = heads, scale
         return out
@@ -54,7 +80,7 @@ class _Attention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse = ctx.saved_tensors
-        dqkv = native().attn_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, ctx.heads, ctx.scale)
+        dqkv = _binding("attn_bwd", qkv.dtype)(qkv, out, dout.contiguous().to(qkv.dtype), lse, ctx.heads, ctx.scale)
         return dqkv, None
 
 
@@ -63,7 +89,7 @@ class _StreamingAttention(torch.autograd.Function):
     def forward(ctx, qkv, heads: int):
         qkv = qkv.contiguous()
         scale = 1.0 / math.sqrt(64)
-        out, lse = native().attn_stream_fwd(qkv, heads, scale)
+        out, lse = _binding("attn_stream_fwd", qkv.dtype)(qkv, heads, scale)
         ctx.save_for_backward(qkv, out, lse)
         ctx.heads, ctx.scale = heads, scale
         return out
@@ -71,7 +97,8 @@ class _StreamingAttention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse = ctx.saved_tensors
-        dqkv = native().attn_stream_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, ctx.heads, ctx.scale)
+        dqkv = _binding("attn_stream_bwd", qkv.dtype)(qkv, out, dout.contiguous().to(qkv.dtype), lse, ctx.heads,
+                                                       ctx.scale)
         return dqkv, None
 
 
