@@ -1525,6 +1525,94 @@ Tensor colsum_rows(Tensor part, int64_t out_kind) {
   return out;
 }
 
+// ---- depthwise convolutions (dwconv_kernels.hip) ---------------------------------------------
+// A channels_last [N, C, H, W] activation: 16-bit (returns its kind) or, if f32_ok, fp32 (*f32).
+int dw_act(const Tensor& t, const char* name, bool f32_ok, bool* f32) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 4 && t.is_contiguous(at::MemoryFormat::ChannelsLast), name,
+              " must be a channels_last [N, C, H, W] GPU tensor");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
+  TORCH_CHECK(t.size(0) <= 65535 && t.size(1) <= 65535 * 64 && t.size(2) * t.size(3) < (1ll << 31), name,
+              ": batch, channels or image too large for the launch grid");
+  if (f32) *f32 = t.scalar_type() == at::kFloat;
+  if (f32_ok && t.scalar_type() == at::kFloat) return 0;
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kHalf, name, " must be bf16 or fp16",
+              f32_ok ? " (or fp32)" : "");
+  return t.scalar_type() == at::kBFloat16 ? 1 : 2;
+}
+
+// The [C, 1, K, K] 16-bit weight of a C-channel depthwise conv: its kind, K through *K.
+int dw_weight(const Tensor& w, int64_t C, int* K, const char* name) {
+  TORCH_CHECK(w.is_cuda() && w.dim() == 4 && w.size(0) == C && w.size(1) == 1 && w.size(2) == w.size(3) &&
+                  w.is_contiguous(), name, ": weight must be a contiguous [C, 1, K, K] GPU tensor");
+  TORCH_CHECK(dpt::dwconv_supported(C, w.size(2)), name, ": C % 8 == 0 and K in {3, 5, 7}, got C ", C, " K ",
+              w.size(2));
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16 || w.scalar_type() == at::kHalf, name, ": weight must be bf16 or fp16");
+  *K = (int)w.size(2);
+  return w.scalar_type() == at::kBFloat16 ? 1 : 2;
+}
+
+// y = dwconv(x, w) + bias: x fp32 or w's type, bias fp32 or w's type, y in w's type.
+Tensor dwconv_fwd(Tensor x, Tensor w, c10::optional<Tensor> bias) {
+  bool f32 = false;
+  const int xk = dw_act(x, "dwconv_fwd: x", true, &f32);
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  int K = 0;
+  const int kind = dw_weight(w, C, &K, "dwconv_fwd");
+  TORCH_CHECK(f32 || xk == kind, "dwconv_fwd: x must be fp32 or of the weight's type");
+  const void* bp = nullptr;
+  int bk = 0;
+  if (bias.has_value() && bias->defined()) {
+    bk = param_kind(*bias, C, "dwconv_fwd: bias");
+    TORCH_CHECK(bk == 0 || bk == kind, "dwconv_fwd: bias must be fp32 or of the weight's type");
+    bp = bias->data_ptr();
+  }
+  auto y = at::empty(x.sizes(), x.options().dtype(w.scalar_type()).memory_format(at::MemoryFormat::ChannelsLast));
+  if (y.numel() == 0) return y;
+  c10::hip::HIPGuard guard(x.device().index());
+  dpt::launch_dwconv(kind, K, f32, false, x.data_ptr(), static_cast<const uint16_t*>(w.data_ptr()), bp, bk,
+                     y.data_ptr(), N, (int)H, (int)W, (int)C, cur_stream(x));
+  return y;
+}
+
+// dx = dwconv(dy, flipped w), written as fp32 when x was fp32.
+Tensor dwconv_dgrad(Tensor dy, Tensor w, bool x_is_f32) {
+  const int dk = dw_act(dy, "dwconv_dgrad: grad", false, nullptr);
+  const int64_t N = dy.size(0), C = dy.size(1), H = dy.size(2), W = dy.size(3);
+  int K = 0;
+  const int kind = dw_weight(w, C, &K, "dwconv_dgrad");
+  TORCH_CHECK(dk == kind, "dwconv_dgrad: grad must be of the weight's type");
+  auto dx = at::empty(dy.sizes(), dy.options().dtype(x_is_f32 ? at::kFloat : dy.scalar_type())
+                                      .memory_format(at::MemoryFormat::ChannelsLast));
+  if (dx.numel() == 0) return dx;
+  c10::hip::HIPGuard guard(dy.device().index());
+  dpt::launch_dwconv(kind, K, x_is_f32, true, dy.data_ptr(), static_cast<const uint16_t*>(w.data_ptr()), nullptr, 0,
+                     dx.data_ptr(), N, (int)H, (int)W, (int)C, cur_stream(dy));
+  return dx;
+}
+
+// Returns {dw [C, 1, K, K], db [C]} of out_kind (0 f32 / 1 bf16 / 2 f16): fp32 partials per pixel
+// slice, then the fixed-order column sum over the slices (colsum_rows: 16 waves per 64 outputs;
+// sum_partials walks the slices serially per output, 65 us per call at S = 256 on an MI355X).
+std::vector<Tensor> dwconv_wgrad(Tensor dy, Tensor x, int64_t K, int64_t out_kind) {
+  bool f32 = false;
+  const int kind = dw_act(dy, "dwconv_wgrad: grad", false, nullptr);
+  const int xk = dw_act(x, "dwconv_wgrad: x", true, &f32);
+  TORCH_CHECK(x.sizes() == dy.sizes() && (f32 || xk == kind), "dwconv_wgrad: x must match grad (fp32 or its type)");
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(dpt::dwconv_supported(C, K) && N * H * W > 0, "dwconv_wgrad: C % 8 == 0, K in {3, 5, 7}, got C ", C,
+              " K ", K);
+  TORCH_CHECK(out_kind >= 0 && out_kind <= 2, "dwconv_wgrad: out kind 0..2");
+  const int S = dpt::dwconv_wgrad_slices(N, (int)H, (int)W, (int)C);
+  const int64_t n = C * K * K + C;
+  auto part = at::empty({(int64_t)S, n}, x.options().dtype(at::kFloat).memory_format(at::MemoryFormat::Contiguous));
+  auto out = at::empty({n}, part.options().dtype(out_kind == 0 ? at::kFloat : kind_dtype((int)out_kind)));
+  c10::hip::HIPGuard guard(x.device().index());
+  dpt::launch_dwconv_wgrad(kind, (int)K, f32, static_cast<const uint16_t*>(dy.data_ptr()), x.data_ptr(),
+                           part.data_ptr<float>(), N, (int)H, (int)W, (int)C, S, cur_stream(x));
+  dpt::launch_colsum_rows(part.data_ptr<float>(), S, n, out.data_ptr(), (int)out_kind, cur_stream(x));
+  return {out.narrow(0, 0, C * K * K).view({C, 1, K, K}), out.narrow(0, C * K * K, C)};
+}
+
 // dst.copy_(src) for same-shape 16-bit tensors of <= 5 dims whose last dim is contiguous in
 // both (e.g. attention heads [b,h,s,dh] <-> [b,s,h,dh]): one vectorised strided-row kernel.
 void copy_rows16(Tensor src, Tensor dst) {
@@ -1628,6 +1716,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bias_grad16", &bias_grad16, py::arg("grad"), py::arg("out_kind"));
   m.def("sum_partials", &sum_partials, py::arg("part"), py::arg("out_kind"));
   m.def("colsum_rows", &colsum_rows, py::arg("part"), py::arg("out_kind"));
+  m.def("dwconv_supported", &dpt::dwconv_supported, py::arg("C"), py::arg("K"));
+  m.def("dwconv_tiles", []() { return std::make_pair(dpt::kDwconvTile, dpt::kDwconvSmallTile); },
+        "(large, small) pixel tile edge of the depthwise forward / backward-data kernel");
+  m.def("dwconv_fwd", &dwconv_fwd, py::arg("x"), py::arg("w"), py::arg("bias") = py::none());
+  m.def("dwconv_dgrad", &dwconv_dgrad, py::arg("grad"), py::arg("w"), py::arg("x_is_f32"));
+  m.def("dwconv_wgrad", &dwconv_wgrad, py::arg("grad"), py::arg("x"), py::arg("K"), py::arg("out_kind"));
   m.def("maxpool_fwd", &maxpool_fwd, py::arg("x"), py::arg("k"), py::arg("stride"), py::arg("pad"),
         py::arg("bn_coef") = py::none());
   m.def("gap_bwd", &gap_bwd, py::arg("g"), py::arg("H"), py::arg("W"), py::arg("dtype"));

@@ -229,6 +229,20 @@ void launch_colsum_rows(const float* part, int64_t n, int64_t D, void* out, int 
 void launch_rows_copy16(const uint16_t* src, uint16_t* dst, const int n[4], const int64_t ss[4], const int64_t ds[4],
                         int L, hipStream_t s);
 
+// dwconv_kernels.hip: depthwise KxK "same" convolutions, channels_last [N,H,W,C], C % 8 == 0, K in
+// {3, 5, 7}; kind 1 bf16 / 2 fp16 operands (w [C][K][K], dy, y); act_f32: x (and dx) are fp32.
+constexpr int kDwconvTile = 16;      // pixel tile edge of the forward / backward-data kernel
+constexpr int kDwconvSmallTile = 8;  // ... for images with an edge <= 8
+bool dwconv_supported(int64_t C, int64_t K);
+// forward (dgrad false: in = x, bias of kind 0 f32 / operand kind or nullptr, out = y 16-bit) or
+// backward-data (dgrad true: in = dy 16-bit, taps flipped, no bias, out = dx in x's type)
+void launch_dwconv(int kind, int K, bool act_f32, bool dgrad, const void* in, const uint16_t* w, const void* bias,
+                   int bias_kind, void* out, int64_t N, int H, int W, int C, hipStream_t s);
+int dwconv_wgrad_slices(int64_t N, int H, int W, int C);
+// part [S][C*K*K + C] fp32 (dw as [c][r][s], then db), S = dwconv_wgrad_slices(...); every entry is written
+void launch_dwconv_wgrad(int kind, int K, bool act_f32, const uint16_t* dy, const void* x, float* part, int64_t N,
+                         int H, int W, int C, int S, hipStream_t s);
+
 // conv_kernels.hip: channels_last bf16 implicit-GEMM convolutions (MFMA).  x [N,H,W,C],
 // w [Cout,R,S,C], y [N,Ho,Wo,Cout]; C % 64 == 0, Cout % 64 == 0.  psum/psq (optional): BN
 // partial sums of y per (channel, M-tile), layout [Cout][conv_m_tiles(M)].

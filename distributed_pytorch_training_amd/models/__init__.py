@@ -9,6 +9,7 @@ import torch.nn as nn
 
 from .resnet import ResNet, resnet18, resnet34, resnet50, resnet101
 from .vit import VisionTransformer, vit_b_16
+from .convnext import ConvNeXt, convnext_base, convnext_small, convnext_tiny
 
 MODELS: Dict[str, Callable[..., nn.Module]] = {
     "resnet18": resnet18,
@@ -16,6 +17,9 @@ MODELS: Dict[str, Callable[..., nn.Module]] = {
     "resnet50": resnet50,
     "resnet101": resnet101,
     "vit_b_16": vit_b_16,
+    "convnext_tiny": convnext_tiny,
+    "convnext_small": convnext_small,
+    "convnext_base": convnext_base,
 }
 
 # Expected parameter counts (torchvision parity).
@@ -24,6 +28,7 @@ PARAM_COUNTS = {
     ("resnet18", 1000): 11_689_512,
     ("resnet50", 1000): 25_557_032,
     ("vit_b_16", 1000): 86_567_656,
+    ("convnext_tiny", 1000): 28_589_128,
 }
 
 
@@ -45,4 +50,5 @@ def count_params(model: nn.Module) -> int:
 
 
 __all__ = ["build_model", "count_params", "MODELS", "PARAM_COUNTS", "ResNet", "VisionTransformer",
-           "resnet18", "resnet34", "resnet50", "resnet101", "vit_b_16"]
+           "ConvNeXt", "resnet18", "resnet34", "resnet50", "resnet101", "vit_b_16", "convnext_tiny", "convnext_small",
+           "convnext_base"]

@@ -24,6 +24,7 @@ import torch.nn.functional as F
 
 from ..ops.conv_f32 import NativeConv2d
 from ..ops import conv as native_conv
+from ..ops import dwconv
 
 SHADOW_ATTR = "_dpt_shadow"
 
@@ -52,6 +53,9 @@ class ShadowConv2d(NativeConv2d):
         w, b = sh["weight"], sh.get("bias", self.bias)
         if not self.dpt_native_conv:
             return nn.Conv2d._conv_forward(self, x, w, b)
+        if (self.groups == self.in_channels == self.out_channels
+                and dwconv.supported(x, w, self.stride, self.padding, self.dilation, self.groups)):
+            return dwconv.dwconv2d(x, w, b)    # depthwise (ConvNeXt): reads the fp32 stream as it is
         if b is None and native_conv.supported(x, w, self.stride, self.padding, self.dilation, self.groups,
                                                self.dpt_min_pixels):
             return native_conv.conv2d(x, w, self.stride[0], self.padding[0], self.dpt_bn_stats)
