@@ -1613,6 +1613,125 @@ std::vector<Tensor> dwconv_wgrad(Tensor dy, Tensor x, int64_t K, int64_t out_kin
   return {out.narrow(0, 0, C * K * K).view({C, 1, K, K}), out.narrow(0, C * K * K, C)};
 }
 
+// ---- ConvNeXt block kernels (cnx_kernels.hip) -------------------------------------------------
+// A contiguous [.., C] GPU activation, 16-byte aligned: its kind (0 fp32 if f32_ok, 1 bf16, 2 fp16).
+int cnx_act(const Tensor& t, int64_t C, const char* name, bool f32_ok) {
+  TORCH_CHECK(t.is_cuda() && t.dim() >= 1 && t.is_contiguous() && t.size(-1) == C, name,
+              " must be a contiguous GPU tensor of width ", C);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
+  if (t.scalar_type() == at::kFloat) {
+    TORCH_CHECK(f32_ok, name, " must be bf16 or fp16");
+    return 0;
+  }
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kHalf, name, " must be bf16 or fp16",
+              f32_ok ? " (or fp32)" : "");
+  return t.scalar_type() == at::kBFloat16 ? 1 : 2;
+}
+
+const float* cnx_f32_vec(const Tensor& t, int64_t C, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == C &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be a contiguous fp32 GPU tensor of ",
+              C, " elements");
+  return t.data_ptr<float>();
+}
+
+// Returns {h, mean, rstd}: h = LayerNorm(y) * gamma + beta over the last dim, of out_kind (1 bf16 /
+// 2 fp16); y fp32 or of that type.
+std::vector<Tensor> cnx_ln_fwd(Tensor y, Tensor gamma, Tensor beta, double eps, int64_t out_kind) {
+  TORCH_CHECK(y.dim() >= 1, "cnx_ln_fwd: y needs a channel dim");
+  const int64_t C = y.size(-1);
+  TORCH_CHECK(dpt::cnx_ln_supported(C), "cnx_ln_fwd: width must be one of 96/192/384/768/128/256/512/1024, got ", C);
+  TORCH_CHECK(out_kind == 1 || out_kind == 2, "cnx_ln_fwd: output kind must be 1 (bf16) or 2 (fp16)");
+  const int yk = cnx_act(y, C, "cnx_ln_fwd: y", true);
+  TORCH_CHECK(yk == 0 || yk == out_kind, "cnx_ln_fwd: y must be fp32 or of the output type");
+  const int64_t T = y.numel() / C;
+  const float* gp = cnx_f32_vec(gamma, C, "cnx_ln_fwd: gamma");
+  const float* bp = cnx_f32_vec(beta, C, "cnx_ln_fwd: beta");
+  auto h = at::empty(y.sizes(), y.options().dtype(kind_dtype((int)out_kind)));
+  auto fopt = y.options().dtype(at::kFloat);
+  auto mean = at::empty({T}, fopt), rstd = at::empty({T}, fopt);
+  c10::hip::HIPGuard guard(y.device().index());
+  dpt::launch_cnx_ln_fwd((int)out_kind, yk == 0, y.data_ptr(), gp, bp, static_cast<uint16_t*>(h.data_ptr()),
+                         mean.data_ptr<float>(), rstd.data_ptr<float>(), T, C, (float)eps, cur_stream(y));
+  return {h, mean, rstd};
+}
+
+// Returns {gy, dgamma, dbeta}: gy in y's type, dgamma / dbeta fp32 (per-block partials, then the
+// fixed-order column sum over the blocks).
+std::vector<Tensor> cnx_ln_bwd(Tensor gh, Tensor y, Tensor mean, Tensor rstd, Tensor gamma) {
+  TORCH_CHECK(y.dim() >= 1, "cnx_ln_bwd: y needs a channel dim");
+  const int64_t C = y.size(-1);
+  TORCH_CHECK(dpt::cnx_ln_supported(C), "cnx_ln_bwd: unsupported width ", C);
+  const int kind = cnx_act(gh, C, "cnx_ln_bwd: grad_h", false);
+  const int yk = cnx_act(y, C, "cnx_ln_bwd: y", true);
+  TORCH_CHECK(gh.sizes() == y.sizes() && (yk == 0 || yk == kind), "cnx_ln_bwd: y must match grad_h (fp32 or its type)");
+  const int64_t T = y.numel() / C;
+  TORCH_CHECK(T > 0, "cnx_ln_bwd: no rows");
+  auto fopt = y.options().dtype(at::kFloat);
+  TORCH_CHECK(mean.is_cuda() && rstd.is_cuda() && mean.scalar_type() == at::kFloat && rstd.scalar_type() == at::kFloat &&
+                  mean.is_contiguous() && rstd.is_contiguous() && mean.numel() == T && rstd.numel() == T,
+              "cnx_ln_bwd: mean / rstd must be contiguous fp32 with one entry per row");
+  const float* gp = cnx_f32_vec(gamma, C, "cnx_ln_bwd: gamma");
+  const int64_t nb = dpt::cnx_ln_bwd_blocks(T, C);
+  auto gy = at::empty_like(y);
+  auto part = at::empty({nb, 2 * C}, fopt);
+  auto dgb = at::empty({2 * C}, fopt);
+  c10::hip::HIPGuard guard(y.device().index());
+  dpt::launch_cnx_ln_bwd(kind, yk == 0, static_cast<const uint16_t*>(gh.data_ptr()), y.data_ptr(),
+                         mean.data_ptr<float>(), rstd.data_ptr<float>(), gp, gy.data_ptr(), part.data_ptr<float>(), T, C,
+                         cur_stream(y));
+  dpt::launch_colsum_rows(part.data_ptr<float>(), nb, 2 * C, dgb.data_ptr(), 0, cur_stream(y));
+  return {gy, dgb.narrow(0, 0, C), dgb.narrow(0, C, C)};
+}
+
+// out = x + ls * (z + b2) in fp32: x fp32 or z's type, z 16-bit, b2 fp32 or z's type, ls fp32.
+Tensor cnx_scale_residual_fwd(Tensor x, Tensor z, Tensor b2, Tensor ls) {
+  TORCH_CHECK(z.dim() >= 1, "cnx_scale_residual_fwd: z needs a channel dim");
+  const int64_t C = z.size(-1);
+  TORCH_CHECK(dpt::cnx_scale_residual_supported(C), "cnx_scale_residual_fwd: C % 8 == 0, got ", C);
+  const int kind = cnx_act(z, C, "cnx_scale_residual_fwd: z", false);
+  const int xk = cnx_act(x, C, "cnx_scale_residual_fwd: x", true);
+  TORCH_CHECK(x.sizes() == z.sizes() && (xk == 0 || xk == kind), "cnx_scale_residual_fwd: x must match z (fp32 or its type)");
+  const int bk = param_kind(b2, C, "cnx_scale_residual_fwd: b2");
+  TORCH_CHECK((bk == 0 || bk == kind) && reinterpret_cast<uintptr_t>(b2.data_ptr()) % 16 == 0,
+              "cnx_scale_residual_fwd: b2 must be fp32 or of z's type, 16-byte aligned");
+  const float* lp = cnx_f32_vec(ls, C, "cnx_scale_residual_fwd: ls");
+  auto out = at::empty(x.sizes(), x.options().dtype(at::kFloat));
+  c10::hip::HIPGuard guard(x.device().index());
+  dpt::launch_cnx_scale_residual_fwd(kind, xk == 0, x.data_ptr(), static_cast<const uint16_t*>(z.data_ptr()),
+                                     b2.data_ptr(), bk, lp, out.data_ptr<float>(), z.numel() / C, C, cur_stream(x));
+  return out;
+}
+
+// Returns {dz, dls, db2}: dz = ls * dout in z's type, dls fp32, db2 in b2's type.
+std::vector<Tensor> cnx_scale_residual_bwd(Tensor dout, Tensor z, Tensor b2, Tensor ls) {
+  TORCH_CHECK(z.dim() >= 1, "cnx_scale_residual_bwd: z needs a channel dim");
+  const int64_t C = z.size(-1);
+  TORCH_CHECK(dpt::cnx_scale_residual_supported(C), "cnx_scale_residual_bwd: C % 8 == 0, got ", C);
+  const int kind = cnx_act(z, C, "cnx_scale_residual_bwd: z", false);
+  TORCH_CHECK(cnx_act(dout, C, "cnx_scale_residual_bwd: grad", true) == 0 && dout.sizes() == z.sizes(),
+              "cnx_scale_residual_bwd: grad must be fp32 and match z");
+  const int bk = param_kind(b2, C, "cnx_scale_residual_bwd: b2");
+  TORCH_CHECK((bk == 0 || bk == kind) && reinterpret_cast<uintptr_t>(b2.data_ptr()) % 16 == 0,
+              "cnx_scale_residual_bwd: b2 must be fp32 or of z's type, 16-byte aligned");
+  const float* lp = cnx_f32_vec(ls, C, "cnx_scale_residual_bwd: ls");
+  const int64_t T = z.numel() / C;
+  TORCH_CHECK(T > 0, "cnx_scale_residual_bwd: no rows");
+  const int64_t nb = dpt::cnx_scale_residual_bwd_blocks(T, C);
+  auto fopt = z.options().dtype(at::kFloat);
+  auto dz = at::empty_like(z);
+  auto part = at::empty({2, nb, C}, fopt);
+  auto dls = at::empty({C}, fopt);
+  auto db2 = at::empty({C}, z.options().dtype(b2.scalar_type()));
+  c10::hip::HIPGuard guard(z.device().index());
+  dpt::launch_cnx_scale_residual_bwd(kind, dout.data_ptr<float>(), static_cast<const uint16_t*>(z.data_ptr()),
+                                     b2.data_ptr(), bk, lp, static_cast<uint16_t*>(dz.data_ptr()),
+                                     part.data_ptr<float>(), T, C, cur_stream(z));
+  dpt::launch_colsum_rows(part.data_ptr<float>(), nb, C, dls.data_ptr(), 0, cur_stream(z));
+  dpt::launch_colsum_rows(part.data_ptr<float>() + nb * C, nb, C, db2.data_ptr(), bk, cur_stream(z));
+  return {dz, dls, db2};
+}
+
 // dst.copy_(src) for same-shape 16-bit tensors of <= 5 dims whose last dim is contiguous in
 // both (e.g. attention heads [b,h,s,dh] <-> [b,s,h,dh]): one vectorised strided-row kernel.
 void copy_rows16(Tensor src, Tensor dst) {
@@ -1722,6 +1841,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dwconv_fwd", &dwconv_fwd, py::arg("x"), py::arg("w"), py::arg("bias") = py::none());
   m.def("dwconv_dgrad", &dwconv_dgrad, py::arg("grad"), py::arg("w"), py::arg("x_is_f32"));
   m.def("dwconv_wgrad", &dwconv_wgrad, py::arg("grad"), py::arg("x"), py::arg("K"), py::arg("out_kind"));
+  m.def("cnx_ln_supported", &dpt::cnx_ln_supported, py::arg("C"));
+  m.def("cnx_ln_geometry", [](int64_t C) { return std::make_pair(dpt::cnx_ln_rows_per_block(C), dpt::kCnxMaxBlocks); },
+        py::arg("C"), "(rows a block handles per pass, most blocks of the backward) of the channel LayerNorm");
+  m.def("cnx_scale_residual_geometry",
+        [](int64_t C) { return std::make_pair(dpt::cnx_scale_residual_rows_per_block(C), dpt::kCnxMaxBlocks); },
+        py::arg("C"), "(rows a block handles per pass, most blocks of the backward) of the block tail");
+  m.def("cnx_ln_fwd", &cnx_ln_fwd, py::arg("y"), py::arg("gamma"), py::arg("beta"), py::arg("eps"),
+        py::arg("out_kind"));
+  m.def("cnx_ln_bwd", &cnx_ln_bwd, py::arg("grad_h"), py::arg("y"), py::arg("mean"), py::arg("rstd"),
+        py::arg("gamma"));
+  m.def("cnx_scale_residual_fwd", &cnx_scale_residual_fwd, py::arg("x"), py::arg("z"), py::arg("b2"), py::arg("ls"));
+  m.def("cnx_scale_residual_bwd", &cnx_scale_residual_bwd, py::arg("grad"), py::arg("z"), py::arg("b2"),
+        py::arg("ls"));
   m.def("maxpool_fwd", &maxpool_fwd, py::arg("x"), py::arg("k"), py::arg("stride"), py::arg("pad"),
         py::arg("bn_coef") = py::none());
   m.def("gap_bwd", &gap_bwd, py::arg("g"), py::arg("H"), py::arg("W"), py::arg("dtype"));

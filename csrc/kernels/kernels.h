@@ -243,6 +243,29 @@ int dwconv_wgrad_slices(int64_t N, int H, int W, int C);
 void launch_dwconv_wgrad(int kind, int K, bool act_f32, const uint16_t* dy, const void* x, float* part, int64_t N,
                          int H, int W, int C, int S, hipStream_t s);
 
+// cnx_kernels.hip: ConvNeXt block kernels over row-major [T, C] views of channels_last activations;
+// kind 1 bf16 / 2 fp16 for the 16-bit tensors, gamma / beta / ls fp32, b2 of kind 0 / 1 / 2.
+constexpr int kCnxMaxBlocks = 512;  // blocks of the two backward kernels: about two per CU
+bool cnx_ln_supported(int64_t C);   // 96 / 192 / 384 / 768 and 128 / 256 / 512 / 1024
+int cnx_ln_rows_per_block(int64_t C);  // rows a block handles per pass: 4 waves x 64 / LANES
+int cnx_ln_bwd_blocks(int64_t T, int64_t C);
+// h = LayerNorm(y) * gamma + beta (16-bit), mean / rstd [T] fp32; y 16-bit or (in_f32) fp32
+void launch_cnx_ln_fwd(int kind, bool in_f32, const void* y, const float* gamma, const float* beta, uint16_t* h,
+                       float* mean, float* rstd, int64_t T, int64_t C, float eps, hipStream_t s);
+// gy (y's type) and part [cnx_ln_bwd_blocks(T, C)][2C] fp32 = column sums of gh * xhat | gh; every entry is written
+void launch_cnx_ln_bwd(int kind, bool in_f32, const uint16_t* gh, const void* y, const float* mean, const float* rstd,
+                       const float* gamma, void* gy, float* part, int64_t T, int64_t C, hipStream_t s);
+bool cnx_scale_residual_supported(int64_t C);  // C % 8 == 0
+int cnx_scale_residual_rows_per_block(int64_t C);
+int cnx_scale_residual_bwd_blocks(int64_t T, int64_t C);
+// out = x + ls * (z + b2) (fp32); x fp32 (x_f32) or 16-bit, z 16-bit
+void launch_cnx_scale_residual_fwd(int kind, bool x_f32, const void* x, const uint16_t* z, const void* b2, int b2_kind,
+                                   const float* ls, float* out, int64_t T, int64_t C, hipStream_t s);
+// dz = 16-bit(ls * dout) and part [2][cnx_scale_residual_bwd_blocks(T, C)][C] fp32 = column sums of
+// dout * (z + b2), then of ls * dout; every entry is written
+void launch_cnx_scale_residual_bwd(int kind, const float* dout, const uint16_t* z, const void* b2, int b2_kind,
+                                   const float* ls, uint16_t* dz, float* part, int64_t T, int64_t C, hipStream_t s);
+
 // conv_kernels.hip: channels_last bf16 implicit-GEMM convolutions (MFMA).  x [N,H,W,C],
 // w [Cout,R,S,C], y [N,Ho,Wo,Cout]; C % 64 == 0, Cout % 64 == 0.  psum/psq (optional): BN
 // partial sums of y per (channel, M-tile), layout [Cout][conv_m_tiles(M)].

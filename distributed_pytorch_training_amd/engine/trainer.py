@@ -95,6 +95,8 @@ class Trainer:
         args = self.args
         from ..models.vit import set_native as vit_set_native
         vit_set_native(model, self.device.type == "cuda")   # fused ViT encoder (no-op for other models)
+        from ..models.convnext import set_native as convnext_set_native
+        convnext_set_native(model, self.device.type == "cuda")   # ConvNeXt blocks and channel LayerNorms
         gpu_cl = self.device.type == "cuda" and bool(getattr(args, "channels_last", False))
         # MFMA convs need channels_last bf16/fp16 activations; routing is per model
         use_native_conv = gpu_cl and bool(getattr(args, "native_conv", True)) and native_conv.ENABLED

@@ -15,8 +15,18 @@ MI355X notes
 * Under bf16 / fp16 autocast with weight shadows and channels_last activations the depthwise
   convs run csrc/kernels/dwconv_kernels.hip (ops/dwconv.py, routed by parallel/shadow.py): the
   block's input is the fp32 residual stream, which the kernels read as it is.
-* Everything else stays on the modules it is built from (``nn.LayerNorm``, ``nn.Linear``,
-  ``nn.GELU``, the stem and downsample ``nn.Conv2d``).
+* In the native engine (``set_native``; a freshly built model and the stock engine stay module by
+  module) a block under bf16 / fp16 autocast on channels_last GPU activations runs the
+  depthwise conv, ``channel_layer_norm16`` (ops/convnext.py,
+  csrc/kernels/cnx_kernels.hip: LayerNorm over the channels of the conv's 16-bit output, several
+  rows per wave, written as the 16-bit GEMM operand), ``linear16`` and ``gelu_linear16`` of
+  ops/vit.py (bias-free fc1, bias + GELU, fc2 with the fused backward where ``dim % 64 == 0``),
+  and ``scale_residual`` (``x + layer_scale * (fc2 + bias)`` in one fp32 pass whose backward
+  also gives the layer-scale and bias gradients).  ``LayerNorm2d`` (stem, downsamples,
+  classifier) takes ``channel_layer_norm16`` too and hands 16 bits to the conv / Linear that
+  follows.  Widths: 96 / 192 / 384 / 768 and 128 / 256 / 512 / 1024; ``DPT_NATIVE_CNBLOCK=0``
+  switches the route off (profiles/convnext_block.md).
+* The stem and downsample ``nn.Conv2d`` have a bias and stay on MIOpen.
 """
 from __future__ import annotations
 
@@ -26,11 +36,32 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..ops import convnext as cnx
+from ..ops.vit import gelu_linear16, linear16
+from ..parallel.shadow import shadow_param
+from .vit import _bias16
+
+
+def _native_route(mod: nn.Module, x: torch.Tensor, dim: int) -> bool:
+    """The conditions of the native block / LayerNorm route (module docstring)."""
+    if not (mod.dpt_native and cnx.ENABLED and x.is_cuda and x.dim() == 4):
+        return False
+    if not (torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") in (torch.bfloat16, torch.float16)):
+        return False
+    return x.is_contiguous(memory_format=torch.channels_last) and cnx.ln_supported(x, dim)
+
 
 class LayerNorm2d(nn.LayerNorm):
     """LayerNorm over the channels of an [N, C, H, W] tensor (a view change for channels_last)."""
+    dpt_native = False   # set_native: channel_layer_norm16, 16-bit output
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if _native_route(self, x, self.normalized_shape[0]):
+            dt = torch.get_autocast_dtype("cuda")
+            rows = x.permute(0, 2, 3, 1)
+            if rows.dtype not in (dt, torch.float32):
+                rows = rows.float()
+            return cnx.channel_layer_norm16(rows, self.weight, self.bias, self.eps, dt).permute(0, 3, 1, 2)
         x = F.layer_norm(x.permute(0, 2, 3, 1), self.normalized_shape, self.weight, self.bias, self.eps)
         return x.permute(0, 3, 1, 2)
 
@@ -45,6 +76,8 @@ class Permute(nn.Module):
 
 
 class CNBlock(nn.Module):
+    dpt_native = False   # set_native: the fused route of _forward_native
+
     def __init__(self, dim: int, layer_scale: float) -> None:
         super().__init__()
         self.block = nn.Sequential(
@@ -59,7 +92,22 @@ class CNBlock(nn.Module):
         self.layer_scale = nn.Parameter(torch.ones(dim, 1, 1) * layer_scale)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if _native_route(self, x, self.layer_scale.shape[0]):
+            return self._forward_native(x)
         return x + self.layer_scale * self.block(x)
+
+    def _forward_native(self, x: torch.Tensor) -> torch.Tensor:
+        dt = torch.get_autocast_dtype("cuda")
+        ln, fc1, fc2 = self.block[2], self.block[3], self.block[5]
+        y = self.block[0](x)                              # depthwise conv: 16-bit, channels_last
+        h = cnx.channel_layer_norm16(y.permute(0, 2, 3, 1), ln.weight, ln.bias, ln.eps, dt)
+        u = linear16(h, shadow_param(fc1, "weight", h))   # biases move into the next kernels
+        z = gelu_linear16(u, _bias16(fc1, "bias", h), shadow_param(fc2, "weight", h))
+        xr = x.permute(0, 2, 3, 1)
+        if xr.dtype not in (dt, torch.float32):
+            xr = xr.float()
+        out = cnx.scale_residual(xr, z, _bias16(fc2, "bias", h), self.layer_scale.flatten())
+        return out.permute(0, 3, 1, 2)
 
 
 class ConvNeXt(nn.Module):
@@ -85,6 +133,18 @@ class ConvNeXt(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.classifier(self.avgpool(self.features(x)))
+
+
+def set_native(model: nn.Module, on: bool = True) -> int:
+    """Route a ConvNeXt's blocks and channel LayerNorms through the native kernels (on) or the
+    modules they are built from (off, the default of a freshly built model); returns how many
+    modules were switched."""
+    n = 0
+    for m in model.modules():
+        if isinstance(m, (CNBlock, LayerNorm2d)):
+            m.dpt_native = bool(on)
+            n += 1
+    return n
 
 
 def convnext_tiny(num_classes: int = 1000, **kw) -> ConvNeXt:
