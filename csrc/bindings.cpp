@@ -1613,6 +1613,106 @@ std::vector<Tensor> dwconv_wgrad(Tensor dy, Tensor x, int64_t K, int64_t out_kin
   return {out.narrow(0, 0, C * K * K).view({C, 1, K, K}), out.narrow(0, C * K * K, C)};
 }
 
+// ---- patchify convolutions (patchconv_kernels.hip) --------------------------------------------
+// The 16-bit [Cout, C, k, k] weight in the kernels' [Cout][k][k][C] order (a copy only when the
+// weight is not channels_last already); its kind, k, C, Cout through the pointers.
+Tensor pc_weight(const Tensor& w, int* kind, int64_t* k, int64_t* C, int64_t* Cout, const char* name) {
+  TORCH_CHECK(w.is_cuda() && w.dim() == 4 && w.size(2) == w.size(3), name, ": weight must be a [Cout, C, k, k] GPU tensor");
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16 || w.scalar_type() == at::kHalf, name, ": weight must be bf16 or fp16");
+  *kind = w.scalar_type() == at::kBFloat16 ? 1 : 2;
+  *Cout = w.size(0); *C = w.size(1); *k = w.size(2);
+  TORCH_CHECK(dpt::patchconv_supported(*C, *Cout, *k), name, ": k = 2 with C % 32 == 0 or k = 4 with C == 3, and ",
+              "Cout % 32 == 0; got k ", *k, " C ", *C, " Cout ", *Cout);
+  Tensor wc = w.contiguous(at::MemoryFormat::ChannelsLast);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(wc.data_ptr()) % 16 == 0, name, ": weight must be 16-byte aligned");
+  return wc;
+}
+
+// rows of the GEMM; the kernels index them with 32-bit integers
+int64_t pc_rows(int64_t N, int64_t H, int64_t W, int64_t k, const char* name) {
+  const int64_t M = N * (H / k) * (W / k);
+  TORCH_CHECK(M < (1ll << 31) - 128 && H < (1 << 24) && W < (1 << 24), name, ": too many output pixels");
+  return M;
+}
+
+// y = patchconv(x, w) + bias: k = 2: x of w's type; k = 4: x fp32 or of w's type; y in w's type.
+Tensor patchconv_fwd(Tensor x, Tensor w, c10::optional<Tensor> bias) {
+  bool f32 = false;
+  const int xk = dw_act(x, "patchconv_fwd: x", true, &f32);
+  int kind = 0;
+  int64_t k = 0, C = 0, Cout = 0;
+  const Tensor wc = pc_weight(w, &kind, &k, &C, &Cout, "patchconv_fwd");
+  const int64_t N = x.size(0), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(x.size(1) == C && (xk == kind || (f32 && k == 4)),
+              "patchconv_fwd: x must have the weight's channels and type (the stem's x may be fp32)");
+  pc_rows(N, H, W, k, "patchconv_fwd");
+  const void* bp = nullptr;
+  int bk = 0;
+  if (bias.has_value() && bias->defined()) {
+    bk = param_kind(*bias, Cout, "patchconv_fwd: bias");
+    TORCH_CHECK(bk == 0 || bk == kind, "patchconv_fwd: bias must be fp32 or of the weight's type");
+    bp = bias->data_ptr();
+  }
+  auto y = at::empty({N, Cout, H / k, W / k},
+                     x.options().dtype(w.scalar_type()).memory_format(at::MemoryFormat::ChannelsLast));
+  if (y.numel() == 0) return y;
+  c10::hip::HIPGuard guard(x.device().index());
+  dpt::launch_patchconv_fwd(kind, f32, x.data_ptr(), static_cast<const uint16_t*>(wc.data_ptr()), bp, bk,
+                            static_cast<uint16_t*>(y.data_ptr()), N, (int)H, (int)W, (int)C, (int)Cout, (int)k,
+                            cur_stream(x));
+  return y;
+}
+
+// dx [N, C, H, W] of a 2x2 stride-2 patchify conv, in dy's type; rows / columns past the last whole
+// patch are zero.
+Tensor patchconv_dgrad(Tensor dy, Tensor w, int64_t H, int64_t W) {
+  const int dk = dw_act(dy, "patchconv_dgrad: grad", false, nullptr);
+  int kind = 0;
+  int64_t k = 0, C = 0, Cout = 0;
+  const Tensor wc = pc_weight(w, &kind, &k, &C, &Cout, "patchconv_dgrad");
+  const int64_t N = dy.size(0);
+  TORCH_CHECK(k == 2 && dk == kind && dy.size(1) == Cout && H >= 0 && W >= 0 && dy.size(2) == H / 2 &&
+                  dy.size(3) == W / 2,
+              "patchconv_dgrad: a 2x2 conv, grad [N, Cout, H/2, W/2] of the weight's type");
+  pc_rows(N, H, W, k, "patchconv_dgrad");
+  auto opt = dy.options().memory_format(at::MemoryFormat::ChannelsLast);
+  if (dy.numel() == 0) return at::zeros({N, C, H, W}, opt);
+  auto dx = at::empty({N, C, H, W}, opt);
+  c10::hip::HIPGuard guard(dy.device().index());
+  dpt::launch_patchconv_dgrad(kind, static_cast<const uint16_t*>(dy.data_ptr()),
+                              static_cast<const uint16_t*>(wc.data_ptr()), static_cast<uint16_t*>(dx.data_ptr()), N,
+                              (int)H, (int)W, (int)C, (int)Cout, cur_stream(dy));
+  return dx;
+}
+
+// Returns {dw [Cout, C, k, k] (channels_last strides), db [Cout]} of out_kind (0 f32 / 1 bf16 /
+// 2 f16): fp32 partials per row slice, summed in a fixed order (sum_partials; the stem: colsum_rows).
+std::vector<Tensor> patchconv_wgrad(Tensor dy, Tensor x, int64_t k, int64_t out_kind) {
+  bool f32 = false;
+  const int kind = dw_act(dy, "patchconv_wgrad: grad", false, nullptr);
+  const int xk = dw_act(x, "patchconv_wgrad: x", true, &f32);
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3), Cout = dy.size(1);
+  TORCH_CHECK(dpt::patchconv_supported(C, Cout, k), "patchconv_wgrad: k = 2 with C % 32 == 0 or k = 4 with C == 3, ",
+              "and Cout % 32 == 0; got k ", k, " C ", C, " Cout ", Cout);
+  TORCH_CHECK(dy.size(0) == N && dy.size(2) == H / k && dy.size(3) == W / k && (xk == kind || (f32 && k == 4)),
+              "patchconv_wgrad: grad must be [N, Cout, H/k, W/k] and x of its type (the stem's x may be fp32)");
+  TORCH_CHECK(out_kind >= 0 && out_kind <= 2, "patchconv_wgrad: out kind 0..2");
+  const int64_t M = pc_rows(N, H, W, k, "patchconv_wgrad");
+  const int64_t K = k * k * C, n = Cout * K + Cout;
+  const int S = dpt::patchconv_wgrad_slices(M, (int)Cout, (int)C, (int)k);
+  auto part = at::empty({(int64_t)S, n}, x.options().dtype(at::kFloat).memory_format(at::MemoryFormat::Contiguous));
+  auto out = at::empty({n}, part.options().dtype(out_kind == 0 ? at::kFloat : kind_dtype((int)out_kind)));
+  c10::hip::HIPGuard guard(x.device().index());
+  dpt::launch_patchconv_wgrad(kind, f32, static_cast<const uint16_t*>(dy.data_ptr()), x.data_ptr(),
+                              part.data_ptr<float>(), N, (int)H, (int)W, (int)C, (int)Cout, (int)k, S, cur_stream(x));
+  // The stem has one tile and hundreds of slices of a few thousand outputs: sum_partials, which walks
+  // the slices serially per output, took 250 us there (S = 512, batch 128); colsum_rows splits them
+  // over 16 waves.  Both add in a fixed order.
+  if (k == 4) dpt::launch_colsum_rows(part.data_ptr<float>(), S, n, out.data_ptr(), (int)out_kind, cur_stream(x));
+  else dpt::launch_sum_partials(part.data_ptr<float>(), n, S, out.data_ptr(), (int)out_kind, cur_stream(x));
+  return {out.narrow(0, 0, Cout * K).view({Cout, k, k, C}).permute({0, 3, 1, 2}), out.narrow(0, Cout * K, Cout)};
+}
+
 // ---- ConvNeXt block kernels (cnx_kernels.hip) -------------------------------------------------
 // A contiguous [.., C] GPU activation, 16-byte aligned: its kind (0 fp32 if f32_ok, 1 bf16, 2 fp16).
 int cnx_act(const Tensor& t, int64_t C, const char* name, bool f32_ok) {
@@ -1841,6 +1941,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dwconv_fwd", &dwconv_fwd, py::arg("x"), py::arg("w"), py::arg("bias") = py::none());
   m.def("dwconv_dgrad", &dwconv_dgrad, py::arg("grad"), py::arg("w"), py::arg("x_is_f32"));
   m.def("dwconv_wgrad", &dwconv_wgrad, py::arg("grad"), py::arg("x"), py::arg("K"), py::arg("out_kind"));
+  m.def("patchconv_supported", &dpt::patchconv_supported, py::arg("C"), py::arg("Cout"), py::arg("k"));
+  m.def("patchconv_tiles", []() { return std::make_pair(dpt::kPatchconvTM, dpt::kPatchconvTN); },
+        "(row tile, column tile) of the patchify conv's forward / backward-data kernels");
+  m.def("patchconv_wgrad_slices", &dpt::patchconv_wgrad_slices, py::arg("M"), py::arg("Cout"), py::arg("C"),
+        py::arg("k"));
+  m.def("patchconv_fwd", &patchconv_fwd, py::arg("x"), py::arg("w"), py::arg("bias") = py::none());
+  m.def("patchconv_dgrad", &patchconv_dgrad, py::arg("grad"), py::arg("w"), py::arg("H"), py::arg("W"));
+  m.def("patchconv_wgrad", &patchconv_wgrad, py::arg("grad"), py::arg("x"), py::arg("k"), py::arg("out_kind"));
   m.def("cnx_ln_supported", &dpt::cnx_ln_supported, py::arg("C"));
   m.def("cnx_ln_geometry", [](int64_t C) { return std::make_pair(dpt::cnx_ln_rows_per_block(C), dpt::kCnxMaxBlocks); },
         py::arg("C"), "(rows a block handles per pass, most blocks of the backward) of the channel LayerNorm");

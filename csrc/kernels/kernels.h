@@ -243,6 +243,26 @@ int dwconv_wgrad_slices(int64_t N, int H, int W, int C);
 void launch_dwconv_wgrad(int kind, int K, bool act_f32, const uint16_t* dy, const void* x, float* part, int64_t N,
                          int H, int W, int C, int S, hipStream_t s);
 
+// patchconv_kernels.hip: patchify convolutions (kernel == stride k, no padding) with bias on the
+// matrix cores, channels_last x [N,H,W,C]; kind 1 bf16 / 2 fp16 operands.  w is [Cout][k][k][C]
+// (a channels_last [Cout, C, k, k] weight); M = N*(H/k)*(W/k) < 2^31 - 128.
+constexpr int kPatchconvTM = 128;  // rows (output pixels) of a forward / backward-data tile
+constexpr int kPatchconvTN = 128;  // columns of a tile, used in 32-column blocks up to Cout
+// k = 2: C % 32 == 0; k = 4 (the stem): C == 3; Cout % 32 == 0
+bool patchconv_supported(int64_t C, int64_t Cout, int64_t k);
+// y [N,H/k,W/k,Cout] = patches(x) w^T + bias (kind 0 f32 / operand kind, or nullptr); x_f32: the
+// stem's x is fp32 and is rounded to the operand type as it is loaded
+void launch_patchconv_fwd(int kind, bool x_f32, const void* x, const uint16_t* w, const void* bias, int bias_kind,
+                          uint16_t* y, int64_t N, int H, int W, int C, int Cout, int k, hipStream_t s);
+// k = 2: dx [N,H,W,C] = dy w scattered back to the patches; every element of dx is written
+void launch_patchconv_dgrad(int kind, const uint16_t* dy, const uint16_t* w, uint16_t* dx, int64_t N, int H, int W,
+                            int C, int Cout, hipStream_t s);
+int patchconv_wgrad_slices(int64_t M, int Cout, int C, int k);
+// part [S][Cout*k*k*C + Cout] fp32 (dw as [co][r][s][c], then db), S = patchconv_wgrad_slices(...);
+// every entry is written
+void launch_patchconv_wgrad(int kind, bool x_f32, const uint16_t* dy, const void* x, float* part, int64_t N, int H,
+                            int W, int C, int Cout, int k, int S, hipStream_t s);
+
 // cnx_kernels.hip: ConvNeXt block kernels over row-major [T, C] views of channels_last activations;
 // kind 1 bf16 / 2 fp16 for the 16-bit tensors, gamma / beta / ls fp32, b2 of kind 0 / 1 / 2.
 constexpr int kCnxMaxBlocks = 512;  // blocks of the two backward kernels: about two per CU

@@ -26,7 +26,10 @@ MI355X notes
   classifier) takes ``channel_layer_norm16`` too and hands 16 bits to the conv / Linear that
   follows.  Widths: 96 / 192 / 384 / 768 and 128 / 256 / 512 / 1024; ``DPT_NATIVE_CNBLOCK=0``
   switches the route off (profiles/convnext_block.md).
-* The stem and downsample ``nn.Conv2d`` have a bias and stay on MIOpen.
+* The stem (4x4 stride 4, reading the fp32 image) and the downsample convs (2x2 stride 2), all with
+  a bias, run csrc/kernels/patchconv_kernels.hip under the same conditions (ops/patchconv.py,
+  routed by parallel/shadow.py): bias and bias gradient in the epilogues, no MIOpen kernel left in
+  the step; ``DPT_NATIVE_PATCHCONV=0`` sends them back to ``F.conv2d`` (profiles/patchconv.md).
 """
 from __future__ import annotations
 

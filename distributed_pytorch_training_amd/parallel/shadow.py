@@ -25,6 +25,7 @@ import torch.nn.functional as F
 from ..ops.conv_f32 import NativeConv2d
 from ..ops import conv as native_conv
 from ..ops import dwconv
+from ..ops import patchconv
 
 SHADOW_ATTR = "_dpt_shadow"
 
@@ -56,6 +57,9 @@ class ShadowConv2d(NativeConv2d):
         if (self.groups == self.in_channels == self.out_channels
                 and dwconv.supported(x, w, self.stride, self.padding, self.dilation, self.groups)):
             return dwconv.dwconv2d(x, w, b)    # depthwise (ConvNeXt): reads the fp32 stream as it is
+        if (b is not None and self.groups == 1 and tuple(self.kernel_size) == tuple(self.stride)
+                and patchconv.supported(x, w, b, self.stride, self.padding, self.dilation, self.groups)):
+            return patchconv.patch_conv2d(x, w, b)    # patchify with bias (ConvNeXt's stem and downsamples)
         if b is None and native_conv.supported(x, w, self.stride, self.padding, self.dilation, self.groups,
                                                self.dpt_min_pixels):
             return native_conv.conv2d(x, w, self.stride[0], self.padding[0], self.dpt_bn_stats)
