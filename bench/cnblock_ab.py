@@ -112,7 +112,7 @@ def kernels_table(C, a, dev):
                   f"{100 * tbs / COPY_TBS:.0f} |", flush=True)
 
 
-def step_ab(a, dev):
+def step_ab(a, dev, model="convnext_tiny", title="ConvNeXt-T"):
     from distributed_pytorch_training_amd.config import parse_args
     from distributed_pytorch_training_amd.data import SyntheticLoader
     from distributed_pytorch_training_amd.engine.trainer import Trainer
@@ -121,10 +121,10 @@ def step_ab(a, dev):
     from distributed_pytorch_training_amd.utils.env import setup_tunableop
 
     setup_tunableop()
-    args = parse_args(["--model", "convnext_tiny", "--dataset", "synthetic", "--batch-size", str(a.batch), "--amp",
+    args = parse_args(["--model", model, "--dataset", "synthetic", "--batch-size", str(a.batch), "--amp",
                        "--amp-dtype", "bf16", "--channels-last", "--no-cuda-graph"])
     torch.manual_seed(0)
-    tr = Trainer(build_model("convnext_tiny", 1000, dev, channels_last=True), args, 0, 1, dev, log=lambda s: None)
+    tr = Trainer(build_model(model, 1000, dev, channels_last=True), args, 0, 1, dev, log=lambda s: None)
     batches = list(iter(SyntheticLoader(a.batch * 4, a.batch, 224, 1000, dev, channels_last=True, pool=4, seed=0)))
 
     def run(n):
@@ -146,7 +146,7 @@ def step_ab(a, dev):
             torch.cuda.synchronize()
             times[on].append(1e3 * (time.time() - t0) / a.steps)
     cnx.ENABLED = True
-    print(f"\nConvNeXt-T step, batch {a.batch}, 224 px, bf16 autocast, channels_last, eager launches; median of "
+    print(f"\n{title} step, batch {a.batch}, 224 px, bf16 autocast, channels_last, eager launches; median of "
           f"{a.rounds} interleaved windows of {a.steps} steps:\n")
     print("| DPT_NATIVE_CNBLOCK | ms / step | img/s | all windows (ms) |\n|---|---|---|---|")
     for on in (True, False):

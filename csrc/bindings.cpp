@@ -1832,6 +1832,77 @@ std::vector<Tensor> cnx_scale_residual_bwd(Tensor dout, Tensor z, Tensor b2, Ten
   return {dz, dls, db2};
 }
 
+// ---- GELU + Global Response Normalization (grn_kernels.hip) ------------------------------------
+// u [.., D] with rows_per_sample rows per sample: its kind; N and D through the pointers.
+int grn_act(const Tensor& u, int64_t rows_per_sample, int64_t* N, int64_t* D, const char* name) {
+  TORCH_CHECK(u.dim() >= 1, name, ": u needs a channel dim");
+  *D = u.size(-1);
+  TORCH_CHECK(dpt::cnx_grn_supported(*D), name, ": D % 8 == 0, got ", *D);
+  const int kind = cnx_act(u, *D, name, false);
+  const int64_t T = u.numel() / *D;
+  TORCH_CHECK(rows_per_sample >= 1 && T >= 1 && T % rows_per_sample == 0 && T / rows_per_sample < (1ll << 31) - 1, name,
+              ": ", T, " rows are not whole samples of ", rows_per_sample, " rows");
+  *N = T / rows_per_sample;
+  return kind;
+}
+
+int grn_bias(const Tensor& b1, int64_t D, int kind, const char* name) {
+  const int bk = param_kind(b1, D, name);
+  TORCH_CHECK((bk == 0 || bk == kind) && reinterpret_cast<uintptr_t>(b1.data_ptr()) % 16 == 0, name,
+              ": b1 must be fp32 or of u's type, 16-byte aligned");
+  return bk;
+}
+
+// Returns {g, G, inv, s}: g = gamma * (y * Nx) + beta + y in u's type, y = GELU(u + b1); G [N, D] the
+// norms over a sample's rows, inv [N] = 1 / (mean_D G + eps), s [N, D] = 1 + gamma * Nx (fp32).
+std::vector<Tensor> cnx_grn_fwd(Tensor u, Tensor b1, Tensor gamma, Tensor beta, int64_t rows_per_sample, double eps) {
+  int64_t N = 0, D = 0;
+  const int kind = grn_act(u, rows_per_sample, &N, &D, "cnx_grn_fwd");
+  const int bk = grn_bias(b1, D, kind, "cnx_grn_fwd");
+  const float* gp = cnx_f32_vec(gamma, D, "cnx_grn_fwd: gamma");
+  const float* bp = cnx_f32_vec(beta, D, "cnx_grn_fwd: beta");
+  auto fopt = u.options().dtype(at::kFloat);
+  auto g = at::empty_like(u);
+  auto part = at::empty({N * dpt::cnx_grn_slices(N, rows_per_sample, D), D}, fopt);
+  auto G = at::empty({N, D}, fopt), inv = at::empty({N}, fopt), s = at::empty({N, D}, fopt);
+  c10::hip::HIPGuard guard(u.device().index());
+  dpt::launch_cnx_grn_fwd(kind, static_cast<const uint16_t*>(u.data_ptr()), b1.data_ptr(), bk, gp, bp,
+                          static_cast<uint16_t*>(g.data_ptr()), part.data_ptr<float>(), G.data_ptr<float>(),
+                          inv.data_ptr<float>(), s.data_ptr<float>(), N, rows_per_sample, D, (float)eps, cur_stream(u));
+  return {g, G, inv, s};
+}
+
+// Returns {du, db1, dgamma, dbeta}: du in u's type, db1 in b1's type, dgamma / dbeta fp32.
+std::vector<Tensor> cnx_grn_bwd(Tensor dg, Tensor u, Tensor b1, Tensor gamma, Tensor G, Tensor inv, Tensor s,
+                                int64_t rows_per_sample) {
+  int64_t N = 0, D = 0;
+  const int kind = grn_act(u, rows_per_sample, &N, &D, "cnx_grn_bwd");
+  TORCH_CHECK(cnx_act(dg, D, "cnx_grn_bwd: grad", false) == kind && dg.sizes() == u.sizes(),
+              "cnx_grn_bwd: grad must match u");
+  const int bk = grn_bias(b1, D, kind, "cnx_grn_bwd");
+  const float* gp = cnx_f32_vec(gamma, D, "cnx_grn_bwd: gamma");
+  const float* Gp = cnx_f32_vec(G, N * D, "cnx_grn_bwd: G");
+  const float* sp = cnx_f32_vec(s, N * D, "cnx_grn_bwd: s");
+  TORCH_CHECK(inv.is_cuda() && inv.scalar_type() == at::kFloat && inv.is_contiguous() && inv.numel() == N,
+              "cnx_grn_bwd: inv must be a contiguous fp32 GPU tensor with one entry per sample");
+  const int64_t nb = N * dpt::cnx_grn_slices(N, rows_per_sample, D);
+  auto fopt = u.options().dtype(at::kFloat);
+  auto du = at::empty_like(u);
+  auto part = at::empty({2, nb, D}, fopt);
+  auto t = at::empty({N, D}, fopt), sn = at::empty({N, D}, fopt);
+  auto dgb = at::empty({2, D}, fopt);
+  auto db1 = at::empty({D}, u.options().dtype(b1.scalar_type()));
+  c10::hip::HIPGuard guard(u.device().index());
+  dpt::launch_cnx_grn_bwd(kind, static_cast<const uint16_t*>(dg.data_ptr()), static_cast<const uint16_t*>(u.data_ptr()),
+                          b1.data_ptr(), bk, gp, Gp, inv.data_ptr<float>(), sp, static_cast<uint16_t*>(du.data_ptr()),
+                          part.data_ptr<float>(), t.data_ptr<float>(), sn.data_ptr<float>(), N, rows_per_sample, D,
+                          cur_stream(u));
+  dpt::launch_colsum_rows(part.data_ptr<float>(), nb, D, db1.data_ptr(), bk, cur_stream(u));
+  dpt::launch_colsum_rows(sn.data_ptr<float>(), N, D, dgb.data_ptr<float>(), 0, cur_stream(u));
+  dpt::launch_colsum_rows(part.data_ptr<float>() + nb * D, nb, D, dgb.data_ptr<float>() + D, 0, cur_stream(u));
+  return {du, db1, dgb.select(0, 0), dgb.select(0, 1)};
+}
+
 // dst.copy_(src) for same-shape 16-bit tensors of <= 5 dims whose last dim is contiguous in
 // both (e.g. attention heads [b,h,s,dh] <-> [b,s,h,dh]): one vectorised strided-row kernel.
 void copy_rows16(Tensor src, Tensor dst) {
@@ -1962,6 +2033,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cnx_scale_residual_fwd", &cnx_scale_residual_fwd, py::arg("x"), py::arg("z"), py::arg("b2"), py::arg("ls"));
   m.def("cnx_scale_residual_bwd", &cnx_scale_residual_bwd, py::arg("grad"), py::arg("z"), py::arg("b2"),
         py::arg("ls"));
+  m.def("cnx_grn_supported", &dpt::cnx_grn_supported, py::arg("D"));
+  m.def("cnx_grn_fwd", &cnx_grn_fwd, py::arg("u"), py::arg("b1"), py::arg("gamma"), py::arg("beta"),
+        py::arg("rows_per_sample"), py::arg("eps"));
+  m.def("cnx_grn_bwd", &cnx_grn_bwd, py::arg("grad"), py::arg("u"), py::arg("b1"), py::arg("gamma"), py::arg("G"),
+        py::arg("inv"), py::arg("s"), py::arg("rows_per_sample"));
   m.def("maxpool_fwd", &maxpool_fwd, py::arg("x"), py::arg("k"), py::arg("stride"), py::arg("pad"),
         py::arg("bn_coef") = py::none());
   m.def("gap_bwd", &gap_bwd, py::arg("g"), py::arg("H"), py::arg("W"), py::arg("dtype"));

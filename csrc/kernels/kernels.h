@@ -286,6 +286,23 @@ void launch_cnx_scale_residual_fwd(int kind, bool x_f32, const void* x, const ui
 void launch_cnx_scale_residual_bwd(int kind, const float* dout, const uint16_t* z, const void* b2, int b2_kind,
                                    const float* ls, uint16_t* dz, float* part, int64_t T, int64_t C, hipStream_t s);
 
+// grn_kernels.hip: bias + GELU + Global Response Normalization (ConvNeXt V2) over u [N, R, D] (16-bit,
+// kind 1 bf16 / 2 fp16), R rows per sample; b1 of kind 0 / 1 / 2, gamma / beta fp32 [D].
+constexpr int kGrnMaxBlocks = 2048;  // blocks of a sweep: about eight per CU
+bool cnx_grn_supported(int64_t D);   // D % 8 == 0
+int cnx_grn_slices(int64_t N, int64_t R, int64_t D);  // row slices per sample (sps)
+// g = gamma * (y * Nx) + beta + y, y = GELU(u + b1).  part [N * sps][D], G [N][D], inv [N] (1 / (mean_D G
+// + eps)) and s [N][D] (1 + gamma * Nx) are fp32; every entry is written.  N, R >= 1.
+void launch_cnx_grn_fwd(int kind, const uint16_t* u, const void* b1, int b1_kind, const float* gamma, const float* beta,
+                        uint16_t* g, float* part, float* G, float* inv, float* s, int64_t N, int64_t R, int64_t D,
+                        float eps, hipStream_t st);
+// du (16-bit) from dg, and fp32 partials whose column sums are the parameter gradients: afterwards
+// part [2][N * sps][D] holds the row sums of du (-> db1) in [0] and of dg (-> dbeta) in [1], sn [N][D] the
+// terms of dgamma; t [N][D] is scratch.  Every entry is written.
+void launch_cnx_grn_bwd(int kind, const uint16_t* dg, const uint16_t* u, const void* b1, int b1_kind,
+                        const float* gamma, const float* G, const float* inv, const float* s, uint16_t* du,
+                        float* part, float* t, float* sn, int64_t N, int64_t R, int64_t D, hipStream_t st);
+
 // conv_kernels.hip: channels_last bf16 implicit-GEMM convolutions (MFMA).  x [N,H,W,C],
 // w [Cout,R,S,C], y [N,Ho,Wo,Cout]; C % 64 == 0, Cout % 64 == 0.  psum/psq (optional): BN
 // partial sums of y per (channel, M-tile), layout [Cout][conv_m_tiles(M)].

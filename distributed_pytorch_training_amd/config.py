@@ -45,7 +45,7 @@ def build_parser() -> argparse.ArgumentParser:
     g = p.add_argument_group("MI355X extensions (defaults reproduce the reference)")
     g.add_argument("--model", default="resnet18",
                    choices=["resnet18", "resnet34", "resnet50", "resnet101", "vit_b_16", "convnext_tiny", "convnext_small",
-                            "convnext_base"],
+                            "convnext_base", "convnextv2_tiny", "convnextv2_base"],
                    help="model architecture")
     g.add_argument("--dataset", default="cifar10", choices=["cifar10", "synthetic"],
                    help="cifar10 reads local CIFAR-10 files; synthetic generates on-device data")

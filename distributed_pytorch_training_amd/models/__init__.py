@@ -9,7 +9,7 @@ import torch.nn as nn
 
 from .resnet import ResNet, resnet18, resnet34, resnet50, resnet101
 from .vit import VisionTransformer, vit_b_16
-from .convnext import ConvNeXt, convnext_base, convnext_small, convnext_tiny
+from .convnext import ConvNeXt, ConvNeXtV2, convnext_base, convnext_small, convnext_tiny, convnextv2_base, convnextv2_tiny
 
 MODELS: Dict[str, Callable[..., nn.Module]] = {
     "resnet18": resnet18,
@@ -20,6 +20,8 @@ MODELS: Dict[str, Callable[..., nn.Module]] = {
     "convnext_tiny": convnext_tiny,
     "convnext_small": convnext_small,
     "convnext_base": convnext_base,
+    "convnextv2_tiny": convnextv2_tiny,
+    "convnextv2_base": convnextv2_base,
 }
 
 # Expected parameter counts (torchvision parity).
@@ -29,6 +31,7 @@ PARAM_COUNTS = {
     ("resnet50", 1000): 25_557_032,
     ("vit_b_16", 1000): 86_567_656,
     ("convnext_tiny", 1000): 28_589_128,
+    ("convnextv2_tiny", 1000): 28_635_496,
 }
 
 
@@ -50,5 +53,5 @@ def count_params(model: nn.Module) -> int:
 
 
 __all__ = ["build_model", "count_params", "MODELS", "PARAM_COUNTS", "ResNet", "VisionTransformer",
-           "ConvNeXt", "resnet18", "resnet34", "resnet50", "resnet101", "vit_b_16", "convnext_tiny", "convnext_small",
-           "convnext_base"]
+           "ConvNeXt", "ConvNeXtV2", "resnet18", "resnet34", "resnet50", "resnet101", "vit_b_16", "convnext_tiny", "convnext_small",
+           "convnext_base", "convnextv2_tiny", "convnextv2_base"]

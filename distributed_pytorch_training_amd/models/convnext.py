@@ -30,6 +30,15 @@ MI355X notes
   a bias, run csrc/kernels/patchconv_kernels.hip under the same conditions (ops/patchconv.py,
   routed by parallel/shadow.py): bias and bias gradient in the epilogues, no MIOpen kernel left in
   the step; ``DPT_NATIVE_PATCHCONV=0`` sends them back to ``F.conv2d`` (profiles/patchconv.md).
+
+ConvNeXt V2 (``convnextv2_tiny`` 28,635,496 parameters at 1000 classes, ``convnextv2_base``) keeps this
+layout and swaps the block: no layer scale, and Global Response Normalization between the MLP's
+GELU and fc2.  ``CNBlockV2`` names its parameters as the official checkpoints do (``dwconv``,
+``norm``, ``pwconv1``, ``grn.gamma`` / ``grn.beta`` of shape [1, 1, 1, 4 dim], ``pwconv2``); the
+containers around the blocks are the V1 ones above.  Its native route, under the same conditions, is
+the depthwise conv, ``channel_layer_norm16``, ``linear16`` (bias-free fc1), ``gelu_grn16``
+(ops/convnext.py, csrc/kernels/grn_kernels.hip: bias + GELU + GRN without storing the GELU's
+output), ``linear16`` (fc2) and ``scale_residual`` with a unit scale (profiles/convnext_v2_grn.md).
 """
 from __future__ import annotations
 
@@ -114,6 +123,10 @@ class CNBlock(nn.Module):
 
 
 class ConvNeXt(nn.Module):
+    @staticmethod
+    def make_block(dim: int, layer_scale: float) -> nn.Module:
+        return CNBlock(dim, layer_scale)
+
     def __init__(self, depths: Sequence[int], dims: Sequence[int], num_classes: int = 1000,
                  layer_scale: float = 1e-6, stochastic_depth_prob: float = 0.0) -> None:
         super().__init__()
@@ -121,7 +134,7 @@ class ConvNeXt(nn.Module):
             raise NotImplementedError("stochastic depth is not implemented (rate must be 0)")
         layers = [nn.Sequential(nn.Conv2d(3, dims[0], kernel_size=4, stride=4), LayerNorm2d(dims[0], eps=1e-6))]
         for i, (depth, dim) in enumerate(zip(depths, dims)):
-            layers.append(nn.Sequential(*[CNBlock(dim, layer_scale) for _ in range(depth)]))
+            layers.append(nn.Sequential(*[self.make_block(dim, layer_scale) for _ in range(depth)]))
             if i + 1 < len(dims):
                 layers.append(nn.Sequential(LayerNorm2d(dim, eps=1e-6),
                                             nn.Conv2d(dim, dims[i + 1], kernel_size=2, stride=2)))
@@ -138,13 +151,88 @@ class ConvNeXt(nn.Module):
         return self.classifier(self.avgpool(self.features(x)))
 
 
+class GRN(nn.Module):
+    """Global Response Normalization over an [N, H, W, D] activation (ConvNeXt V2): parameters
+    ``gamma`` / ``beta`` [1, 1, 1, D] start at zero, so a fresh layer is the identity."""
+
+    def __init__(self, dim: int, eps: float = 1e-6) -> None:
+        super().__init__()
+        self.gamma = nn.Parameter(torch.zeros(1, 1, 1, dim))
+        self.beta = nn.Parameter(torch.zeros(1, 1, 1, dim))
+        self.eps = eps
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        gx = torch.linalg.vector_norm(x, ord=2, dim=(1, 2), keepdim=True)
+        nx = gx / (gx.mean(dim=-1, keepdim=True) + self.eps)
+        return self.gamma * (x * nx) + self.beta + x
+
+
+_ONES = {}   # (device, dim) -> fp32 ones: the unit layer scale of a V2 block's tail
+
+
+def _ones(dim: int, device: torch.device) -> torch.Tensor:
+    key = (device, dim)
+    if key not in _ONES:
+        _ONES[key] = torch.ones(dim, device=device)
+    return _ONES[key]
+
+
+class CNBlockV2(nn.Module):
+    """A ConvNeXt V2 block with the official checkpoint's parameter names: ``dwconv``, ``norm``,
+    ``pwconv1``, ``grn.gamma`` / ``grn.beta``, ``pwconv2``; no layer scale."""
+    dpt_native = False   # set_native: the fused route of _forward_native
+
+    def __init__(self, dim: int) -> None:
+        super().__init__()
+        self.dwconv = nn.Conv2d(dim, dim, kernel_size=7, padding=3, groups=dim, bias=True)
+        self.norm = nn.LayerNorm(dim, eps=1e-6)
+        self.pwconv1 = nn.Linear(dim, 4 * dim)
+        self.act = nn.GELU()
+        self.grn = GRN(4 * dim)
+        self.pwconv2 = nn.Linear(4 * dim, dim)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        dim = self.norm.normalized_shape[0]
+        if _native_route(self, x, dim) and cnx.grn_supported(x, 4 * dim):
+            return self._forward_native(x)
+        y = self.norm(self.dwconv(x).permute(0, 2, 3, 1))
+        y = self.pwconv2(self.grn(self.act(self.pwconv1(y))))
+        return x + y.permute(0, 3, 1, 2)
+
+    def _forward_native(self, x: torch.Tensor) -> torch.Tensor:
+        dt = torch.get_autocast_dtype("cuda")
+        ln, fc1, fc2 = self.norm, self.pwconv1, self.pwconv2
+        y = self.dwconv(x)                                # depthwise conv: 16-bit, channels_last
+        h = cnx.channel_layer_norm16(y.permute(0, 2, 3, 1), ln.weight, ln.bias, ln.eps, dt)
+        u = linear16(h, shadow_param(fc1, "weight", h))   # biases move into the next kernels
+        g = cnx.gelu_grn16(u, _bias16(fc1, "bias", h), self.grn.gamma.flatten(), self.grn.beta.flatten(),
+                           u.shape[1] * u.shape[2], self.grn.eps)
+        z = linear16(g, shadow_param(fc2, "weight", h))
+        xr = x.permute(0, 2, 3, 1)
+        if xr.dtype not in (dt, torch.float32):
+            xr = xr.float()
+        out = cnx.scale_residual(xr, z, _bias16(fc2, "bias", h), _ones(z.shape[-1], z.device))
+        return out.permute(0, 3, 1, 2)
+
+
+class ConvNeXtV2(ConvNeXt):
+    """ConvNeXt V2: the V1 layout (``features`` / ``classifier``) with CNBlockV2 blocks."""
+    @staticmethod
+    def make_block(dim: int, layer_scale: float) -> nn.Module:
+        return CNBlockV2(dim)
+
+    def __init__(self, depths: Sequence[int], dims: Sequence[int], num_classes: int = 1000,
+                 stochastic_depth_prob: float = 0.0) -> None:
+        super().__init__(depths, dims, num_classes, 0.0, stochastic_depth_prob)
+
+
 def set_native(model: nn.Module, on: bool = True) -> int:
     """Route a ConvNeXt's blocks and channel LayerNorms through the native kernels (on) or the
     modules they are built from (off, the default of a freshly built model); returns how many
     modules were switched."""
     n = 0
     for m in model.modules():
-        if isinstance(m, (CNBlock, LayerNorm2d)):
+        if isinstance(m, (CNBlock, CNBlockV2, LayerNorm2d)):
             m.dpt_native = bool(on)
             n += 1
     return n
@@ -160,3 +248,11 @@ def convnext_small(num_classes: int = 1000, **kw) -> ConvNeXt:
 
 def convnext_base(num_classes: int = 1000, **kw) -> ConvNeXt:
     return ConvNeXt([3, 3, 27, 3], [128, 256, 512, 1024], num_classes, **kw)
+
+
+def convnextv2_tiny(num_classes: int = 1000, **kw) -> ConvNeXtV2:
+    return ConvNeXtV2([3, 3, 9, 3], [96, 192, 384, 768], num_classes, **kw)
+
+
+def convnextv2_base(num_classes: int = 1000, **kw) -> ConvNeXtV2:
+    return ConvNeXtV2([3, 3, 27, 3], [128, 256, 512, 1024], num_classes, **kw)

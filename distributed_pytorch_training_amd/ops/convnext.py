@@ -1,4 +1,4 @@
-"""ConvNeXt block ops on the gfx950 kernels of csrc/kernels/cnx_kernels.hip.
+"""ConvNeXt block ops on the gfx950 kernels of csrc/kernels/cnx_kernels.hip and grn_kernels.hip.
 
 * ``channel_layer_norm16(y, weight, bias, eps, dtype)``  LayerNorm over the last (channel) dim of
   a channels-last activation viewed as [.., C], written directly in ``dtype`` (bf16 / fp16): y is
@@ -8,6 +8,11 @@
   bias (16-bit), x the residual stream (fp32; 16-bit directly after a stem / downsample conv).
   The backward writes dz = ls * dout and the column sums for dls and db2 in one pass; the
   residual gradient is dout itself.
+* ``gelu_grn16(u, b1, gamma, beta, rows_per_sample, eps)``  ConvNeXt V2's bias + GELU + Global
+  Response Normalization between fc1 and fc2: y = GELU(u + b1), G = ||y||_2 over the
+  ``rows_per_sample`` rows of a sample, Nx = G / (mean over D of G + eps), g = gamma * (y * Nx) +
+  beta + y in u's 16-bit type.  u [.., D] is fc1's output WITHOUT its bias.  y is not stored: the
+  backward recomputes it from u and keeps only the per-(sample, channel) statistics.
 
 Semantics equal the PyTorch composition under autocast up to rounding order.  CPU tensors run
 that composition through the same signatures; an unsupported GPU input raises (no quiet
@@ -78,3 +83,39 @@ def scale_residual(x: torch.Tensor, z: torch.Tensor, b2: torch.Tensor, ls: torch
     global CALLS
     CALLS += 1
     return _ScaleResidual.apply(x.contiguous(), z.contiguous(), b2.contiguous(), ls.contiguous())
+
+
+class _GeluGrn16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, b1, gamma, beta, rows_per_sample, eps):
+        g, G, inv, s = native().cnx_grn_fwd(u, b1, gamma, beta, int(rows_per_sample), float(eps))
+        ctx.save_for_backward(u, b1, gamma, G, inv, s)
+        ctx.rows_per_sample = int(rows_per_sample)
+        return g
+
+    @staticmethod
+    def backward(ctx, dg):
+        u, b1, gamma, G, inv, s = ctx.saved_tensors
+        du, db1, dgamma, dbeta = native().cnx_grn_bwd(dg.contiguous(), u, b1, gamma, G, inv, s, ctx.rows_per_sample)
+        return du, db1, dgamma, dbeta, None, None
+
+
+def grn_supported(x: torch.Tensor, dim: int) -> bool:
+    return x.is_cuda and native_available() and native().cnx_grn_supported(dim)
+
+
+def gelu_grn16(u: torch.Tensor, b1: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, rows_per_sample: int,
+               eps: float = 1e-6) -> torch.Tensor:
+    """GRN(GELU(u + b1)) in u's dtype for u [.., D] whose rows come in samples of ``rows_per_sample``;
+    b1, gamma, beta [D] (gamma / beta fp32 on the GPU)."""
+    D = u.shape[-1]
+    if not u.is_cuda:
+        ct = torch.promote_types(u.dtype, torch.float32)     # 16-bit operands compute in fp32
+        y = F.gelu(u.to(ct) + b1.to(ct)).reshape(-1, rows_per_sample, D)
+        G = torch.linalg.vector_norm(y, ord=2, dim=1, keepdim=True)
+        Nx = G / (G.mean(dim=-1, keepdim=True) + eps)
+        return (gamma.to(ct) * (y * Nx) + beta.to(ct) + y).reshape(u.shape).to(u.dtype)
+    global CALLS
+    CALLS += 1
+    return _GeluGrn16.apply(u.contiguous(), b1.contiguous(), gamma.contiguous(), beta.contiguous(),
+                            rows_per_sample, eps)
